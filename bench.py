@@ -2,6 +2,7 @@
 """Benchmark: batched Treasure Game env-steps/s on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--envs ENVS_PER_GPU]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -23,13 +24,26 @@ masked) so that the batch is in its steady state when timing starts: the envs' p
 their MT19937 generations are spread out, so the timed steps regenerate generations at the
 steady-state rate (N x draws per env-step / 312 per step; the line reports the measured and
 the expected rate), and episodes complete and flow through the gather at their steady-state
-rate (the first episodes end after ~550 masked / ~2,000 uniform steps).  The gathered records
-of global envs [0, E) are compared with the oracle's replay of those envs over every step of
-the run (``episode_check``).
+rate (the first episodes end after ~550 masked / ~2,000 uniform steps).
 
-Prints ONE JSON line (rank 0) with the driver's fields plus ``roofline`` (tg_step's kernels:
-algorithmic bytes per launch over their HIP-event-timed duration vs the 8 TB/s HBM peak),
-``cpu_baseline`` (the C oracle timed on this box's host cores, a bounded sample) and, at
+A plain run does only that: set-up, the untimed steps, the K timed steps, and ONE JSON line
+(rank 0) with the driver's fields (``value``, ``ms_per_step`` = the wall time of the timed
+region / K, ...) plus ``roofline`` (tg_step's kernels: algorithmic bytes per launch over their
+duration, taken from the timed steps themselves, vs the 8 TB/s HBM peak).
+
+``--dump-outputs DIR`` writes what the LAST timed step returned to its caller (rank 0's shard),
+after timing, as DIR/<name>.npy: ``obs`` (float64 [n, 9]), ``reward`` (float64 [n]), ``valid``,
+``done`` (float32 [n]) and, for c5, ``frames`` (float32 [n, H, W, 3]); with --rollout K the last
+row of the rollout's reward / valid / done.  Batches whose arrays would exceed 48 MB (the files
+stay under 64 MB) are sampled: the same seeded choice of envs for every array, listed in
+``env_index`` (float64 [n], the global env indices).  The seeds of the envs and of the action stream are fixed, so the same
+arguments give the same arrays from run to run and from build to build.
+
+``--full`` adds everything else the benchmark measures or checks, each in runs of its own after
+the headline: ``episode_check`` (the gathered records of global envs [0, E) compared with the
+oracle's replay of those envs over every step of the run), ``region_probe`` (the timed
+region's launches as empty kernels), ``cpu_baseline`` (the C oracle timed on this box's host
+cores, a bounded sample) and, at
 N = 1, ``parity_check`` (4,096 envs x 200 steps replayed on the GPU and compared bit-for-bit
 with the oracle's run in the cpu_baseline leg), ``masked_policy`` (the same measurement
 with the masked-uniform policy: every step runs an option) and ``dropin_n1`` (the N = 1
@@ -60,6 +74,8 @@ ACTION_SEED = 0x5EED0001
 PREGEN_BYTES = 8 << 30  # pre-generated action rows for the timed steps, at most this much HBM
 EP_CAP = 4096          # episode records gathered per rank per step of a drain interval (padded)
 KST_MAX = 512          # step launches whose kernel spans the library records (tg_amd.hip)
+DUMP_BYTES = 48 << 20  # --dump-outputs: the arrays' bytes in all (under 64 MB with room to spare)
+DUMP_SEED = 0xD0          # and the seed of the env sample taken beyond that
 # algorithmic bytes of one tg_step for THIS data layout, per kernel:
 #   k_classify, every env: action 4 + state word 16 + angles 16 + episode 8 read (44)
 #     reward-None env: obs 72 + reward/valid/done 6 written (78; its episode word holds the
@@ -132,6 +148,13 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the other measurements and checks: the "
+                         "masked-policy line, the N = 1 drop-in, the CPU baselines, the parity "
+                         "and episode checks against the oracle, the empty-kernel region probe")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / "
+                         "float64, at most 64 MB in all: a seeded sample of the envs beyond that)")
     ap.add_argument("--burn-in", type=int, default=None,
                     help="untimed steps after the warm-up so that MT regenerations and episode "
                          "completions reach their steady-state rates (default 3000 uniform / "
@@ -174,15 +197,15 @@ def parse(argv=None):
                     help="wait for the timed region's end in torch.cuda.synchronize alone (the "
                          "default polls the end event first, then synchronizes)")
     ap.add_argument("--secondary-steps", type=int, default=30,
-                    help="N = 1, c3: steps of the masked-policy line (0 disables it)")
+                    help="--full, N = 1, c3: steps of the masked-policy line (0 disables it)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
-                    help="target duration of the CPU-baseline sample (0 disables it and the "
-                         "parity check)")
+                    help="--full: target duration of the CPU-baseline sample (0 disables it "
+                         "and the parity check)")
     ap.add_argument("--traffic-json", default=None,
                     help="PMC-derived HBM bytes per tg_step (default profiles/"
                          "traffic_step_<policy>.json), if measured")
     ap.add_argument("--episode-envs", type=int, default=None,
-                    help="episode_check: the oracle replays global envs [0, E) over the whole "
+                    help="--full: episode_check, the oracle replays global envs [0, E) over the whole "
                          "run (default 16384 uniform / 8192 masked; 0 disables)")
     return ap.parse_args(argv)
 
@@ -348,7 +371,7 @@ class Runner:
 
     def __init__(self, tg, D, args, policy, count, offset, world, dev, keep_log):
         self.tg, self.D, self.args, self.world, self.dev = tg, D, args, world, dev
-        self.count = count
+        self.count, self.offset, self.roll_k = count, offset, 0
         self.autoreset = not args.no_autoreset
         vec = tg.TreasureGameVec(count, seed=0, global_offset=offset, autoreset=False, device=dev,
                                  level_dir=args.level)
@@ -435,6 +458,7 @@ class Runner:
         self.tg._lib.check(self.L.tg_rollout(self.h, k, ACTION_SEED, t, self.pol, self.flags,
                                              None, None, p(self.roll[0]), p(self.roll[1]),
                                              p(self.roll[2]), self.stream), "rollout")
+        self.roll_k = k
         self.drain()
 
     def advance(self, t, nsteps):
@@ -578,7 +602,7 @@ class Runner:
                         "spin": bool(self.args.spin)}
         self.timing = False
         vec.set_timing(0)
-        self.region_probe = self.probe_region(steps)
+        self.region_probe = self.probe_region(steps) if self.args.full else None
         st = vec.stats()
         self.drain_all(log=True)  # records of the timed steps still queued (untimed)
         if self.world > 1:
@@ -586,6 +610,34 @@ class Runner:
             dist.all_reduce(dt_t, op=dist.ReduceOp.MAX)
             dt = float(dt_t.item())
         return dt, st
+
+    def outputs(self):
+        """What the last step handed its caller (--dump-outputs), as float32 / float64 host
+        arrays by name: tg_step's obs / reward / valid / done (c5: and tg_render's frames), or
+        the last row of tg_rollout's reward / valid / done.  At most DUMP_BYTES in all: beyond
+        that, the same seeded sample of the envs for every array.  ``env_index`` holds the
+        global indices of the envs kept."""
+        vec = self.vec
+        if self.K:
+            row = max(self.roll_k, 1) - 1
+            src = [("reward", self.roll[0][row], np.float64), ("valid", self.roll[1][row], np.float32),
+                   ("done", self.roll[2][row], np.float32)]
+        else:
+            src = [("obs", vec._obs, np.float64), ("reward", vec._rew, np.float64),
+                   ("valid", vec._valid, np.float32), ("done", vec._done, np.float32)]
+            if self.frames is not None:
+                src.append(("frames", self.frames, np.float32))
+        per_env = 8 + sum(t[0].numel() * np.dtype(d).itemsize for _, t, d in src)
+        keep = int(min(self.count, max(DUMP_BYTES // per_env, 1)))
+        idx = np.arange(self.count)
+        if keep < self.count:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(self.count, keep, replace=False))
+        sel = torch.from_numpy(idx).to(self.dev)
+        torch.cuda.synchronize(self.dev)
+        out = {"env_index": (idx + self.offset).astype(np.float64)}
+        for name, t, d in src:
+            out[name] = t.index_select(0, sel).cpu().numpy().astype(d)
+        return out
 
 
 def node_totals(st, world, dev):
@@ -796,7 +848,7 @@ def main():
     autoreset = run.autoreset
     # (policy, warmup, burn-in, steps, E, the gathered records of envs [0, E) and their digest)
     checks = []
-    if rank == 0 and autoreset and ep_envs > 0:
+    if rank == 0 and args.full and autoreset and ep_envs > 0:
         checks.append((args.policy, args.warmup, args.burn_in_used, args.steps, ep_envs,
                        run.log.digest(env_below=ep_envs), "line"))
 
@@ -856,10 +908,14 @@ def main():
         line.update({"episodes": node["episodes"], "episodes_dropped": node["episodes_dropped"],
                      "episodes_gathered": rec, "episode_digest": digest,
                      "gather_every": run.G, "error_flags": errs})
+    if rank == 0 and args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in run.outputs().items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
     run.vec.close()
     del run
 
-    if rank == 0 and world == 1 and not c5 and args.secondary_steps > 0:
+    if rank == 0 and args.full and world == 1 and not c5 and args.secondary_steps > 0:
         # the masked-uniform policy: every step runs an option (report it beside
         # the uniform headline), same batch size, its own burn-in
         other = "masked" if args.policy == "uniform" else "uniform"
@@ -887,7 +943,7 @@ def main():
         line[other + "_policy"] = sec
         line["dropin_n1"] = dropin_latency(tg)
 
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if rank == 0 and args.full and world == 1 and args.cpu_seconds > 0:
         if c5:
             line["cpu_baseline"] = cpu_baseline_render(args.cpu_seconds, args.policy)
         else:

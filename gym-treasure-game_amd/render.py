@@ -2,7 +2,8 @@
 
 The renderer (libtg_amd.so ``tg_render_init`` / ``tg_render``) takes the reference's sprites
 as one RGBA8 sheet in ``TG_SPR_*`` order.  The sprites are the reference's art, not shipped
-here (the hero, handle and key are Braid assets used with permission, see the reference's
+with the package (a copy for the tests is under tests/golden/sprites; the hero, handle and
+key are Braid assets used with permission, see the reference's
 sprites/attribution.txt): ``load_sprites`` decodes them from an installed
 gym_treasure_game (or any directory with the same layout) with PIL, the same RGBA decode
 pygame's ``image.load().convert_alpha()`` gives for these PNGs.  ``synthetic_sprites`` makes a

@@ -112,12 +112,14 @@ def test_composition_vs_oracle_other_level_size(hostcheck, oracle):
     np.testing.assert_array_equal(got, want)
 
 
+SPRITES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sprites")
+
+
 def test_real_sprites_if_present(hostcheck, oracle):
-    d = R.default_sprite_dir() or "/root/reference/gym_treasure_game/envs/_treasure_game_impl/sprites"
-    try:
-        sprites = R.load_sprites(d)
-    except (FileNotFoundError, OSError, ImportError):
-        pytest.skip("reference sprites not available")
+    """The reference's own sprite sheet: its 24 PNGs are stored under tests/golden/sprites
+    (their licences: attribution.txt there), in the layout load_sprites reads."""
+    sprites = R.load_sprites(SPRITES)
+    assert sprites.shape == (R.SPRITE_COUNT, 32, 32, 4) and sprites.dtype == np.uint8
     envs = np.arange(8)
     got = hc_frames(hostcheck, envs, 40, 3, 1, True, sprites)
     want = oracle.run_render(0, envs, 40, 3, 1, True, sprites)
