@@ -26,6 +26,8 @@ TG_ERR_RENDER = 1 << 28
 TG_ERR_WINDOW = 1 << 29
 TG_ERR_FLOW = 1 << 30
 TG_SPR_COUNT = 24
+TG_FRAME_RGB = 3
+TG_FRAME_GRAY = 1
 OBS_DIM = 9
 NUM_ACTIONS = 9
 
@@ -36,7 +38,7 @@ EXPORTS = ("tg_create", "tg_destroy", "tg_num_envs", "tg_reset", "tg_step", "tg_
            "tg_observe", "tg_policy_actions", "tg_episodes", "tg_errors", "tg_set_mode", "tg_set_timing", "tg_regenerate",
            "tg_set_episode_capacity", "tg_predicate_table",
            "tg_get_stats", "tg_stats_reset", "tg_kernel_info", "tg_mt_layout", "tg_probe_dispatch", "tg_read_state", "tg_write_state", "tg_render_init", "tg_frame_shape",
-           "tg_render", "tg_last_error", "tg_version")
+           "tg_render", "tg_frame_shape_scaled", "tg_render_scaled", "tg_last_error", "tg_version")
 
 
 class TgError(RuntimeError):
@@ -119,6 +121,8 @@ def load():
         "tg_render_init": (i32, [P, P, i32, i32]),
         "tg_frame_shape": (i32, [P, ctypes.POINTER(i32), ctypes.POINTER(i32)]),
         "tg_render": (i32, [P, i64, i64, P, P]),
+        "tg_frame_shape_scaled": (i32, [P, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]),
+        "tg_render_scaled": (i32, [P, i64, i64, i32, i32, P, P]),
         "tg_last_error": (ctypes.c_char_p, []),
         "tg_version": (ctypes.c_char_p, []),
     }

@@ -1,5 +1,6 @@
 // tg_render.hip — TreasureGame.render('rgb_array') for a whole batch (tg_render_init /
-// tg_render / tg_frame_shape of include/tg_amd.h).
+// tg_render / tg_frame_shape of include/tg_amd.h), and the downscaled / grayscale form
+// (tg_frame_shape_scaled / tg_render_scaled, k_render_scaled below).
 //
 // Reference: TG/:98-105 render() -> _TreasureGameDrawer.draw_domain (DR/:136-163) and
 // draw_object (DR/:238-269); ObservationWrapper (TG/:38-51) renders after every reset/step.
@@ -34,6 +35,7 @@
 #include "tg_batch.h"
 #include "tg_level.h"
 #include "tg_render.h"
+#include "tg_render_scaled.h"
 
 namespace tg {
 
@@ -45,6 +47,11 @@ struct RenderState {
   uint4* tiles = nullptr;        // static layer + each cell-aligned sprite, per cell
   uint32_t* spr = nullptr;       // [D_COUNT][48*48] ARGB
   uint64_t knob = 0;             // knob half widths + 1, 4 bits per row dy = -4..4
+  // tg_render_scaled: the host's static layer and sprites (pooled on a scale's first call)
+  // and the per-scale device tables, by scale_index
+  std::vector<uint32_t> bg32, dyn;
+  uint32_t* bg_small[NSCALE] = {};
+  uint32_t* tiles_small[NSCALE] = {};
 };
 
 void render_free(RenderState* rs) {
@@ -52,6 +59,10 @@ void render_free(RenderState* rs) {
   void* bufs[] = {rs->bg, rs->tiles, rs->spr};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
+  for (int i = 0; i < NSCALE; ++i) {
+    if (rs->bg_small[i]) (void)hipFree(rs->bg_small[i]);
+    if (rs->tiles_small[i]) (void)hipFree(rs->tiles_small[i]);
+  }
   delete rs;
 }
 
@@ -132,6 +143,133 @@ __global__ __launch_bounds__(RBLOCK) void k_render(RenderArgs A, const uint4* __
   }
 }
 
+// ---- tg_render_scaled ----------------------------------------------------------------------
+// The frames of a group of SG envs are one run of SG * h * w output pixels; a workgroup takes
+// a span of SSPAN of them and builds it in LDS in three passes:
+//   1. every pixel is classified (scaled_lookup): those a pooled table holds are copied, the
+//      rest (under the hero, a shaft or knob, a two-item cell: a few dozen per env) are queued;
+//   2. the queued boxes are composed at full resolution, one source row of a box per thread
+//      (a box per lane would leave one lane walking s*s dependent loads while 63 wait), the
+//      rows' channel sums added into the box's LDS word;
+//   3. the span is stored, 4 pixels per thread (12 B of RGB or 4 B of gray) as whole dwords:
+//      SG is a multiple of 4, so a group starts on a dword whatever the frame size.  Only a
+//      short last group's tail is stored byte by byte, so nothing outside
+//      [out, out + count * frame bytes) is written.
+constexpr int SG = 4;        // envs per group
+constexpr int SPX = 4;       // pixels per thread per store
+constexpr int SSPAN = 4096;  // output pixels per workgroup
+// Queued boxes per workgroup.  Past it a thread composes its own box inline (scaled_compose:
+// the same rows, summed in the lane).  A span holds about 4096 * 48 / Wpx hero boxes plus as
+// many again per handle, so only a level narrower than about 12 cells can get there: none of
+// the shipped or test levels does, and no GPU test reaches that branch; scaled_compose itself
+// is what the host check runs for every pixel with fast = 0.
+constexpr int SQCAP = 1024;
+
+__device__ __forceinline__ void span_pixel(int p, int fp, int w, int& k, int& x, int& y) {
+  k = p / fp;
+  const int r = p - k * fp;
+  y = r / w, x = r - y * w;
+}
+
+__global__ __launch_bounds__(RBLOCK) void k_render_scaled(ScaledArgs P,
+                                                          const uint4* __restrict__ st4,
+                                                          const double2* __restrict__ angs,
+                                                          int64_t first, int64_t count, int spans,
+                                                          uint8_t* __restrict__ out) {
+  __shared__ Layer lay[SG][NLAYER];
+  __shared__ uint32_t live[SG];
+  __shared__ uint32_t px[SSPAN];             // the span's pixels, XRGB
+  __shared__ unsigned long long acc[SQCAP];  // a queued box's channel sums
+  __shared__ uint16_t queue[SQCAP];          // its pixel within the span
+  __shared__ uint32_t qn;
+  const int tid = (int)threadIdx.x;
+  const int64_t grp = blockIdx.x / spans;
+  const int span = (int)(blockIdx.x - grp * spans);
+  const int64_t e0 = grp * SG;
+  const int ne = (int)(count - e0 < SG ? count - e0 : SG);
+  const int fp = P.h * P.w;  // output pixels per frame
+  const int gpx = ne * fp;   // and in this group
+  const int pb = span * SSPAN;
+  if (pb >= gpx) return;     // a short last group needs fewer spans (block-uniform)
+  const int npx = gpx - pb < SSPAN ? gpx - pb : SSPAN;
+  if (tid < SG) live[tid] = 0u;
+  if (tid == 0) qn = 0u;
+  for (int e = tid; e < SQCAP; e += RBLOCK) acc[e] = 0ull;
+  __syncthreads();
+  if (tid < SG * NLAYER) {
+    const int k = tid / NLAYER, i = tid - k * NLAYER;
+    if (k < ne) {
+      Layer l;
+      bool on = false;
+      const int64_t g = first + e0 + k;
+      const uint32_t err = make_layer(P.A, i, st4[g], angs[g], l, on);
+      if (err) atomicOr(P.A.err, err);
+      if (on && l.x1 > 0 && l.x0 < P.A.Wpx && l.y1 > 0 && l.y0 < P.A.Hpx) {
+        lay[k][i] = l;
+        atomicOr(&live[k], 1u << i);
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < npx; i += RBLOCK) {
+    int k, x, y;
+    span_pixel(pb + i, fp, P.w, k, x, y);
+    const uint32_t hit = pixel_items(P, lay[k], live[k], x, y);
+    uint32_t c;
+    if (!scaled_lookup(P, lay[k], live[k], hit, x, y, c)) {
+      const uint32_t slot = atomicAdd(&qn, 1u);
+      if (slot < (uint32_t)SQCAP) {
+        queue[slot] = (uint16_t)i;
+        continue;
+      }
+      c = scaled_compose(P.A, lay[k], hit, P.s, x, y);
+    }
+    px[i] = c;
+  }
+  __syncthreads();
+  const int nq = (int)(qn < (uint32_t)SQCAP ? qn : (uint32_t)SQCAP);
+  for (int wi = tid; wi < nq * P.s; wi += RBLOCK) {
+    const int e = wi / P.s, dy = wi - e * P.s;
+    int k, x, y;
+    span_pixel(pb + queue[e], fp, P.w, k, x, y);
+    const uint32_t hit = pixel_items(P, lay[k], live[k], x, y);
+    atomicAdd(&acc[e], (unsigned long long)scaled_compose_row(P.A, lay[k], hit, P.s, x, P.s * y + dy));
+  }
+  __syncthreads();
+  for (int e = tid; e < nq; e += RBLOCK) px[queue[e]] = scaled_finish(acc[e], P.s);
+  __syncthreads();
+  uint8_t* const gout = out + (e0 * (int64_t)fp + pb) * P.ch;
+  for (int i0 = tid * SPX; i0 < npx; i0 += RBLOCK * SPX) {
+    const int np = npx - i0 < SPX ? npx - i0 : SPX;
+    uint32_t c[SPX];
+#pragma unroll
+    for (int j = 0; j < SPX; ++j) c[j] = j < np ? px[i0 + j] : 0u;
+    if (P.ch == 3) {
+      uint8_t* d = gout + (int64_t)i0 * 3;
+      const uint32_t a0 = px3(c[0]), a1 = px3(c[1]), a2 = px3(c[2]), a3 = px3(c[3]);
+      if (np == SPX) {
+        uint32_t* d4 = reinterpret_cast<uint32_t*>(d);
+        d4[0] = a0 | (a1 << 24);
+        d4[1] = (a1 >> 8) | (a2 << 16);
+        d4[2] = (a2 >> 16) | (a3 << 8);
+      } else {
+        const uint32_t a[SPX] = {a0, a1, a2, a3};
+        for (int j = 0; j < np; ++j)
+          for (int b = 0; b < 3; ++b) d[3 * j + b] = (uint8_t)(a[j] >> (8 * b));
+      }
+    } else {
+      uint8_t* d = gout + i0;
+      const uint32_t g0 = luma_px(c[0]), g1 = luma_px(c[1]), g2 = luma_px(c[2]), g3 = luma_px(c[3]);
+      if (np == SPX) {
+        *reinterpret_cast<uint32_t*>(d) = g0 | (g1 << 8) | (g2 << 16) | (g3 << 24);
+      } else {
+        const uint32_t a[SPX] = {g0, g1, g2, g3};
+        for (int j = 0; j < np; ++j) d[j] = (uint8_t)a[j];
+      }
+    }
+  }
+}
+
 }  // namespace
 }  // namespace tg
 
@@ -162,6 +300,7 @@ int tg_render_init(tg_batch* h, const uint8_t* sprites, int32_t sw, int32_t sh) 
   const std::vector<uint32_t> dyn = dynamic_sprites(sc);
   const std::vector<uint8_t> tiles = rgb_bytes(cell_tiles(bg32, W, H, dyn));
   RenderState* rs = new RenderState();
+  rs->bg32 = bg32, rs->dyn = dyn;  // kept for tg_render_scaled's pooling
   rs->Wpx = Wpx, rs->Hpx = Hpx, rs->CH = Wpx * 3 / 16;  // W * 144 bytes per row: whole chunks
   rs->knob = knob_table(KNOB_R);
   auto undo = [&](int code) {
@@ -208,6 +347,77 @@ int tg_render(tg_batch* h, int64_t first, int64_t count, uint8_t* rgb, void* str
   if (blocks > 0x7FFFFFFF) return fail(TG_E_INVAL, "tg_render: too many envs in one call");
   hipLaunchKernelGGL(k_render, dim3((unsigned)blocks), dim3(RBLOCK), 0, (hipStream_t)stream, A,
                      h->S.st4, h->S.ang, first, count, reinterpret_cast<uint4*>(rgb));
+  HIP_TRY(hipGetLastError());
+  return TG_OK;
+}
+
+static int scaled_dims(const tg_batch* h, int32_t scale, int* si) {
+  if (!h) return fail(TG_E_INVAL, "null handle");
+  *si = scale_index(scale);
+  if (*si < 0) return fail(TG_E_INVAL, "scale %d is not a divisor of 48", (int)scale);
+  return TG_OK;
+}
+
+int tg_frame_shape_scaled(const tg_batch* h, int32_t scale, int32_t* height, int32_t* width) {
+  int si;
+  if (int rc = scaled_dims(h, scale, &si)) return rc;
+  if (height) *height = h->L.H * RS / scale;
+  if (width) *width = h->L.W * RS / scale;
+  return TG_OK;
+}
+
+int tg_render_scaled(tg_batch* h, int64_t first, int64_t count, int32_t scale, int32_t channels,
+                     uint8_t* out, void* stream) {
+  BIND(h);
+  if (!h->rs) return fail(TG_E_STATE, "tg_render_scaled: call tg_render_init first");
+  int si;
+  if (int rc = scaled_dims(h, scale, &si)) return rc;
+  if (channels != TG_FRAME_RGB && channels != TG_FRAME_GRAY)
+    return fail(TG_E_INVAL, "tg_render_scaled: channels must be TG_FRAME_RGB or TG_FRAME_GRAY");
+  if (first < 0 || count < 0 || first + count > h->n || (count && !out))
+    return fail(TG_E_INVAL, "tg_render_scaled: envs [%lld, %lld) outside [0, %lld)",
+                (long long)first, (long long)(first + count), (long long)h->n);
+  if (((uintptr_t)out & 15u) != 0)
+    return fail(TG_E_INVAL, "tg_render_scaled: out must be 16-B aligned");
+  if (!count) return TG_OK;
+  RenderState* rs = h->rs;
+  const int W = h->L.W, H = h->L.H;
+  if (!rs->bg_small[si]) {  // this scale's first call: pool on the host, upload (synchronises)
+    const std::vector<uint32_t> b = pooled_static(rs->bg32, W, H, scale);
+    const std::vector<uint32_t> t = pooled_tiles(rs->bg32, W, H, rs->dyn, scale);
+    uint32_t *db = nullptr, *dt = nullptr;
+    if (hipMalloc((void**)&db, b.size() * 4) != hipSuccess ||
+        hipMalloc((void**)&dt, t.size() * 4) != hipSuccess) {
+      if (db) (void)hipFree(db);
+      return fail(TG_E_NOMEM, "tg_render_scaled: device allocation failed");
+    }
+    if (hipMemcpy(db, b.data(), b.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dt, t.data(), t.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipFree(db);
+      (void)hipFree(dt);
+      return fail(TG_E_HIP, "tg_render_scaled: upload failed");
+    }
+    rs->bg_small[si] = db, rs->tiles_small[si] = dt;
+  }
+  ScaledArgs P;
+  RenderArgs& A = P.A;
+  A.bg = rs->bg, A.tiles = rs->tiles, A.spr = rs->spr, A.err = h->err;
+  A.Wpx = rs->Wpx, A.Hpx = rs->Hpx, A.CH = rs->CH, A.H = H, A.W = W;
+  A.knob = rs->knob;
+  for (int k = 0; k < 3; ++k) A.door_cx[k] = h->L.door_cx[k], A.door_cy[k] = h->L.door_cy[k];
+  for (int k = 0; k < 2; ++k) A.handle_cx[k] = h->L.handle_cx[k], A.handle_cy[k] = h->L.handle_cy[k];
+  A.bolt_cx = h->L.bolt_cx, A.bolt_cy = h->L.bolt_cy;
+  P.bg_small = rs->bg_small[si], P.tiles_small = rs->tiles_small[si];
+  P.s = scale, P.cs = RS / scale, P.w = rs->Wpx / scale, P.h = rs->Hpx / scale;
+  P.ch = channels, P.fast = 1;  // fast: scaled_pixel's switch (host check); the kernel has none
+  const int64_t group_px = (int64_t)SG * P.h * P.w;
+  if (group_px > 0x7FFFFFFF - SSPAN)
+    return fail(TG_E_INVAL, "tg_render_scaled: frame too large at this scale");
+  const int spans = (int)((group_px + SSPAN - 1) / SSPAN);
+  const int64_t blocks = (count + SG - 1) / SG * spans;
+  if (blocks > 0x7FFFFFFF) return fail(TG_E_INVAL, "tg_render_scaled: too many envs in one call");
+  hipLaunchKernelGGL(k_render_scaled, dim3((unsigned)blocks), dim3(RBLOCK), 0, (hipStream_t)stream,
+                     P, h->S.st4, h->S.ang, first, count, spans, out);
   HIP_TRY(hipGetLastError());
   return TG_OK;
 }

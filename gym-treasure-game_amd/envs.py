@@ -381,9 +381,40 @@ class TreasureGameVec:
               "tg_frame_shape")
         self.frame_shape = (h.value, w.value, 3)
 
-    def render(self, first=0, count=None, out=None):
+    def frame_shape_scaled(self, scale=8, gray=False):
+        """(h, w, c) of ``render(scale=scale, gray=gray)``'s frames: (78, 84, 3) for the default
+        level at scale 8.  ``scale`` must divide 48 (``TgError`` otherwise)."""
+        h, w = ctypes.c_int32(), ctypes.c_int32()
+        check(self._L.tg_frame_shape_scaled(self.handle, int(scale), ctypes.byref(h),
+                                            ctypes.byref(w)), "tg_frame_shape_scaled")
+        return (h.value, w.value, 1 if gray else 3)
+
+    def _render_scaled(self, first, count, out, scale, gray):
+        if getattr(self, "frame_shape", None) is None:
+            self.render_init()
+        count = self.num_envs - first if count is None else int(count)
+        shape = self.frame_shape_scaled(scale, gray)
+        if out is None:
+            out = torch.empty((max(count, 0),) + shape, dtype=torch.uint8, device=self.device)
+        elif (out.dtype != torch.uint8 or not out.is_contiguous() or out.device != self.device
+              or tuple(out.shape) != (count,) + shape):
+            raise ValueError("out must be a contiguous uint8 [%d, %d, %d, %d] tensor on %s"
+                             % ((count,) + shape + (self.device,)))
+        check(self._L.tg_render_scaled(self.handle, int(first), count, int(scale), shape[2],
+                                       _ptr(out), self._stream()), "tg_render_scaled")
+        return out
+
+    def render(self, first=0, count=None, out=None, scale=1, gray=False):
         """render('rgb_array') of envs [first, first+count): uint8 [count, H*48, W*48, 3]
-        on the device (the reference's ``rgb`` array per env, TG/:103-105)."""
+        on the device (the reference's ``rgb`` array per env, TG/:103-105).
+
+        ``scale`` (a divisor of 48) and ``gray`` give the pixel-observation form instead,
+        uint8 [count, H*48/scale, W*48/scale, 3 or 1]: the full frame average-pooled over
+        scale x scale boxes (halves round up), then (77 R + 150 G + 29 B + 128) >> 8 for gray,
+        rendered directly at that size (tg_render_scaled).  The first call for a scale builds
+        its tables and synchronises."""
+        if scale != 1 or gray:
+            return self._render_scaled(first, count, out, scale, gray)
         if getattr(self, "frame_shape", None) is None:
             self.render_init()
         count = self.num_envs - first if count is None else int(count)
@@ -698,13 +729,13 @@ class TreasureGame:
         state, r, done = self._run(a)
         return state, r, done, {}
 
-    def render(self, mode="human"):
+    def render(self, mode="human", scale=1, gray=False):
         if mode != "rgb_array":
             raise NotImplementedError("render(mode=%r): only 'rgb_array' (no display / gym "
                                       "image viewer here, TG/:106-110)" % (mode,))
         if getattr(self._vec, "frame_shape", None) is None:
             self._vec.render_init(self._sprites)
-        return self._vec.render().cpu().numpy()[0]
+        return self._vec.render(scale=scale, gray=gray).cpu().numpy()[0]
 
     def close(self):
         if self.viewer is not None:
@@ -721,14 +752,21 @@ class ObservationWrapper:
     reference.  Over a ``TreasureGameVec`` it is the batch's frames, a uint8 device tensor
     [N, 624, 672, 3] rendered by one kernel launch into a buffer the wrapper owns
     (overwritten each call), and step returns ``(frames, reward, valid, done, info)``.
+
+    ``scale`` (a divisor of 48) and ``gray`` select the downscaled / grayscale frame of
+    ``TreasureGameVec.render``: [N, 78, 84, 1] at ``scale=8, gray=True`` on the default level
+    (an extension: the reference's wrapper renders full size only).
     """
 
-    def __init__(self, env, sprites=None):
+    def __init__(self, env, sprites=None, scale=1, gray=False):
         self.env = env
+        self._scale, self._gray = int(scale), bool(gray)
         self._vec = isinstance(env, TreasureGameVec)
         if self._vec:
             env.render_init(sprites)
-            self._frames = torch.empty((env.num_envs,) + env.frame_shape, dtype=torch.uint8,
+            shape = (env.frame_shape if self._scale == 1 and not self._gray
+                     else env.frame_shape_scaled(self._scale, self._gray))
+            self._frames = torch.empty((env.num_envs,) + shape, dtype=torch.uint8,
                                        device=env.device)
         else:
             if sprites is not None:
@@ -744,8 +782,8 @@ class ObservationWrapper:
 
     def _screen(self):
         if self._vec:
-            return self.env.render(out=self._frames)
-        return self.env.render(mode="rgb_array")
+            return self.env.render(out=self._frames, scale=self._scale, gray=self._gray)
+        return self.env.render(mode="rgb_array", scale=self._scale, gray=self._gray)
 
     def reset(self, **kwargs):
         self.env.reset(**kwargs)

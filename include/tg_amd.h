@@ -331,6 +331,29 @@ int tg_frame_shape(const tg_batch *h, int32_t *height, int32_t *width);
  * 16-B aligned), the screen of each env's current state (after auto-reset, the new episode's). */
 int tg_render(tg_batch *h, int64_t first, int64_t count, uint8_t *rgb, void *stream);
 
+/* ---- downscaled / grayscale frames (an extension: the reference has no such mode) --------
+ * With F the frame tg_render writes and `scale` s a divisor of 48 (1, 2, 3, 4, 6, 8, 12, 16,
+ * 24, 48; anything else is TG_E_INVAL), the RGB output is the box mean with halves rounded up,
+ *   out[y][x][c] = (2 * S + s*s) / (2 * s*s),  S = sum of F[s*y + dy][s*x + dx][c], dy, dx < s,
+ * and the gray output is (77*R + 150*G + 29*B + 128) >> 8 of those averaged bytes.  The items
+ * are composited at full resolution before the sum (the alpha blend does not commute with
+ * averaging), so the result is exactly this function of tg_render's frame; scale 1 with
+ * TG_FRAME_RGB is tg_render's output byte for byte.  TG_ERR_RENDER is raised as by tg_render. */
+#define TG_FRAME_RGB 3
+#define TG_FRAME_GRAY 1
+/* Output size in pixels at `scale`: H*48/scale rows x W*48/scale columns (78 x 84 at 8). */
+int tg_frame_shape_scaled(const tg_batch *h, int32_t scale, int32_t *height, int32_t *width);
+/* Frames of envs [first, first+count): out u8 [count][height][width][channels] (device, 16-B
+ * aligned; a frame need not be a multiple of 16 B and the frames are packed).  Needs
+ * tg_render_init first (TG_E_STATE).  The first call for a scale pools the static layer and
+ * the cell tiles on the host and uploads them (it synchronises); they are cached until the
+ * next tg_render_init or tg_destroy (with a host copy of the static layer and sprites, about
+ * 1.7 MB for the default level, that tg_render_init keeps for this).  Later calls only launch
+ * on `stream`.  Because that first call allocates and copies, it cannot run inside a stream
+ * capture: call each (scale) once before capturing a graph that renders at it. */
+int tg_render_scaled(tg_batch *h, int64_t first, int64_t count, int32_t scale, int32_t channels,
+                     uint8_t *out, void *stream);
+
 const char *tg_last_error(void);
 const char *tg_version(void);
 
