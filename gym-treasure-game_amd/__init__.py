@@ -10,7 +10,8 @@ installed, mirroring gym_treasure_game/__init__.py:3-6.
 """
 from ._lib import TG_ERR_FLOW, TgError  # noqa: F401
 from .envs import (OPTION_NAMES, STATE_NAMES, GpuOption, ObservationWrapper,  # noqa: F401
-                   TreasureGame, TreasureGameVec, TreasureGameVectorEnv, make_vec, read_level)
+                   TreasureGame, TreasureGameVec, TreasureGameVectorEnv, make_vec,
+                   mlp_param_count, pack_mlp_params, read_level)
 from .render import load_sprites, synthetic_sprites  # noqa: F401
 
 __version__ = "0.1.0"

@@ -28,6 +28,12 @@ TG_ERR_FLOW = 1 << 30
 TG_SPR_COUNT = 24
 TG_FRAME_RGB = 3
 TG_FRAME_GRAY = 1
+TG_ACT_RELU = 0
+TG_ACT_TANH = 1
+TG_MLP_SAMPLE = 0
+TG_MLP_GREEDY = 1
+TG_E_INVAL = -1
+TG_E_STATE = -5
 OBS_DIM = 9
 NUM_ACTIONS = 9
 
@@ -38,7 +44,8 @@ EXPORTS = ("tg_create", "tg_destroy", "tg_num_envs", "tg_reset", "tg_step", "tg_
            "tg_observe", "tg_policy_actions", "tg_episodes", "tg_errors", "tg_set_mode", "tg_set_timing", "tg_regenerate",
            "tg_set_episode_capacity", "tg_predicate_table",
            "tg_get_stats", "tg_stats_reset", "tg_kernel_info", "tg_mt_layout", "tg_probe_dispatch", "tg_read_state", "tg_write_state", "tg_render_init", "tg_frame_shape",
-           "tg_render", "tg_frame_shape_scaled", "tg_render_scaled", "tg_last_error", "tg_version")
+           "tg_render", "tg_frame_shape_scaled", "tg_render_scaled", "tg_policy_mlp_load", "tg_policy_mlp",
+           "tg_rollout_mlp", "tg_last_error", "tg_version")
 
 
 class TgError(RuntimeError):
@@ -123,6 +130,9 @@ def load():
         "tg_render": (i32, [P, i64, i64, P, P]),
         "tg_frame_shape_scaled": (i32, [P, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]),
         "tg_render_scaled": (i32, [P, i64, i64, i32, i32, P, P]),
+        "tg_policy_mlp_load": (i32, [P, i32, i32, i32, P, P]),
+        "tg_policy_mlp": (i32, [P, u64, i64, i32, P, P, P, P, P]),
+        "tg_rollout_mlp": (i32, [P, i32, u64, i64, i32, u32, P, P, P, P, P, P, P, P]),
         "tg_last_error": (ctypes.c_char_p, []),
         "tg_version": (ctypes.c_char_p, []),
     }

@@ -16,7 +16,7 @@ FLOW_SRC = os.path.join(HERE, "csrc", "tg_flow.hip")
 FLOW_FLAGS = ["-mllvm", "-disable-machine-licm"]
 DEPS = SRCS + [FLOW_SRC] + [os.path.join(HERE, "csrc", f) for f in ("tg_core.h", "tg_level.h", "tg_batch.h",
                                                         "tg_render.h", "tg_render_scaled.h", "tg_twist.h",
-                                                        "tg_flow.h")] + [
+                                                        "tg_flow.h", "tg_policy_mlp.h")] + [
     os.path.join(os.path.dirname(HERE), "include", "tg_amd.h")]
 OUT = os.path.join(HERE, "libtg_amd.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -30,6 +30,7 @@
 #include "tg_level.h"
 #include "tg_batch.h"
 #include "tg_twist.h"
+#include "tg_policy_mlp.h"
 
 #ifndef TG_FLOW_TU  // (tg_flow.hip includes this file for the device code only)
 namespace tg {
@@ -1363,6 +1364,45 @@ __global__ __launch_bounds__(BLOCK) void k_actions(Soa S, int64_t n, Level L,
   out[i] = policy_action(L, m, e, policy, a0, g0 + i, t);
 }
 
+// The learned actor (tg_policy_mlp.h): one env per lane.  The lane forms its obs row
+// as k_observe does and keeps x, the first layer's activations and the ten head accumulators in
+// VGPRs; the packed parameters sit at a wave-uniform address, so every weight is a scalar load
+// into an SGPR operand of a v_fma_f32 (nothing is written through the scalar path).  masked: the
+// level is staged as k_actions stages it and A is available_mask's bits.  Writes actions and,
+// where given, logp, value and logits [n][9] of envs [0, n) of the view S (g0: env 0's GLOBAL
+// index).  No atomics: two launches on the same state give identical bits.
+template <int H, int ACT>
+__global__ __launch_bounds__(BLOCK) void k_policy_mlp(Soa S, int64_t n, Level L,
+                                                       const uint32_t* __restrict__ grid,
+                                                       const float* __restrict__ params, int masked,
+                                                       int mode, uint64_t a0, int64_t g0, int64_t t,
+                                                       int32_t* __restrict__ actions,
+                                                       float* __restrict__ logp,
+                                                       float* __restrict__ value,
+                                                       float* __restrict__ logits) {
+  __shared__ LdsLevel lv;
+  if (masked) stage_level(lv, grid, L);  // uniform branch
+  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const Map m{reinterpret_cast<const uint8_t*>(lv.grid), L.W, L.H};
+  Env e;
+  unpack(S.st4[i], S.ang[i], e);
+  double o[9];
+  observe(L, e, o);
+  float lg[MLP_OUT], v;
+  mlp_forward<H, ACT>(params, o, lg, v);
+  const uint32_t allowed = mlp_allowed(masked, masked ? available_mask(L, m, e) : 0u);
+  float lp;
+  actions[i] = mlp_select(lg, allowed, mode, mlp_uniform(a0, g0 + i, t), lp);
+  if (logp) logp[i] = lp;
+  if (value) value[i] = v;
+  if (logits) {
+    float* q = logits + i * MLP_OUT;
+#pragma unroll
+    for (int k = 0; k < MLP_OUT; ++k) q[k] = lg[k];
+  }
+}
+
 // move up to `cap` completed-episode records to `out`, keep the rest queued (device only,
 // so the per-step episode gather never waits on the host)
 __global__ __launch_bounds__(BLOCK) void k_drain_episodes(tg_episode* __restrict__ eps,
@@ -2078,7 +2118,8 @@ void tg_destroy(tg_batch* h) {
   render_free(h->rs);
   flow_free(h);
   void* bufs[] = {h->grid, h->genrand, h->gotab, h->masks, h->obs_q, h->S.st4, h->S.ang, h->S.ep,
-                  h->S.mt, h->S.mc, h->eps, h->eps_count, h->err, h->obs_scratch, h->kst};
+                  h->S.mt, h->S.mc, h->eps, h->eps_count, h->err, h->obs_scratch, h->kst,
+                  h->mlp_params, h->mlp_actions};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   free_ctx(h->main);
@@ -2364,6 +2405,25 @@ int launch_flow(tg_batch* h, int k, const FlowIO& io, bool ar, int pol, hipStrea
   }
   c.rpend += k;
   if (c.rpend >= REGEN_STEPS) return launch_regen(h, c, st);
+  return TG_OK;
+}
+// k_policy_mlp over envs [off, off + cnt) of the handle on `st`; the outputs are the whole
+// handle's rows (the range's start at off)
+int launch_policy_mlp(tg_batch* h, int64_t off, int64_t cnt, uint64_t a0, int64_t t, int mode,
+                      int32_t* actions, float* logp, float* value, float* logits, hipStream_t st) {
+  using K = decltype(&k_policy_mlp<16, 0>);
+  static const K kern[4][2] = {{k_policy_mlp<16, 0>, k_policy_mlp<16, 1>},
+                               {k_policy_mlp<32, 0>, k_policy_mlp<32, 1>},
+                               {k_policy_mlp<64, 0>, k_policy_mlp<64, 1>},
+                               {k_policy_mlp<128, 0>, k_policy_mlp<128, 1>}};
+  const int hi = h->mlp_hidden == 16 ? 0 : h->mlp_hidden == 32 ? 1 : h->mlp_hidden == 64 ? 2 : 3;
+  StepCtx view;
+  view.off = off;
+  hipLaunchKernelGGL(kern[hi][h->mlp_act], dim3(grid_for(cnt)), dim3(BLOCK), 0, st, soa_of(h, view),
+                     cnt, h->L, h->grid, h->mlp_params, h->mlp_masked, mode, a0, h->g0 + off, t,
+                     actions + off, logp ? logp + off : nullptr, value ? value + off : nullptr,
+                     logits ? logits + off * MLP_OUT : nullptr);
+  HIP_TRY(hipGetLastError());
   return TG_OK;
 }
 }  // namespace
@@ -2813,6 +2873,92 @@ int tg_rollout(tg_batch* h, int32_t steps, uint64_t action_seed, int64_t t0, int
       // stagger: group g + 1 starts after group g's first k_classify (half a step apart)
       hipEvent_t mid = (s == 0 && h->stagger && g + 1 < h->grp.size()) ? h->grp[g + 1].ev : nullptr;
       if ((rc = launch_step(h, c, io_of(s), ar, c.st, tb + (uint32_t)s, mid))) return rc;
+      if (mid) HIP_TRY(hipStreamWaitEvent(h->grp[g + 1].st, mid, 0));
+    }
+  for (auto& c : h->grp) {
+    if ((rc = launch_regen(h, c, c.st))) return rc;
+    HIP_TRY(hipEventRecord(c.ev, c.st));
+    HIP_TRY(hipStreamWaitEvent(cs, c.ev, 0));
+  }
+  return TG_OK;
+}
+
+int tg_policy_mlp_load(tg_batch* h, int32_t hidden, int32_t act, int32_t masked,
+                       const float* params_dev, void* stream) {
+  BIND(h);
+  if (!mlp_hidden_ok(hidden) || (act != TG_ACT_RELU && act != TG_ACT_TANH) || !params_dev)
+    return fail(TG_E_INVAL, "tg_policy_mlp_load: hidden %d (16, 32, 64, 128), act %d (TG_ACT_*) and "
+                            "a device pointer to the packed parameters", hidden, act);
+  // sized once for the widest network, so a later load never reallocates (or synchronises)
+  if (!h->mlp_params &&
+      hipMalloc((void**)&h->mlp_params, sizeof(float) * (size_t)mlp_param_count(MLP_MAX_HIDDEN)) !=
+          hipSuccess)
+    return fail(TG_E_NOMEM, "tg_policy_mlp_load: parameter buffer");
+  HIP_TRY(hipMemcpyAsync(h->mlp_params, params_dev, sizeof(float) * (size_t)mlp_param_count(hidden),
+                         hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  h->mlp_hidden = hidden;
+  h->mlp_act = act;
+  h->mlp_masked = masked ? 1 : 0;
+  return TG_OK;
+}
+
+int tg_policy_mlp(tg_batch* h, uint64_t a0, int64_t t, int32_t mode, int32_t* actions, float* logp,
+                  float* value, float* logits, void* stream) {
+  BIND(h);
+  if (!h->mlp_hidden) return fail(TG_E_STATE, "tg_policy_mlp: no parameters (tg_policy_mlp_load)");
+  if (!actions || (mode != TG_MLP_SAMPLE && mode != TG_MLP_GREEDY))
+    return fail(TG_E_INVAL, "tg_policy_mlp: bad arguments");
+  return launch_policy_mlp(h, 0, h->n, a0, t, mode, actions, logp, value, logits,
+                           (hipStream_t)stream);
+}
+
+int tg_rollout_mlp(tg_batch* h, int32_t steps, uint64_t a0, int64_t t0, int32_t mode, uint32_t flags,
+                   int32_t* actions, double* obs, int32_t* reward, uint8_t* valid, uint8_t* done,
+                   float* logp, float* value, void* stream) {
+  BIND(h);
+  if (!h->mlp_hidden) return fail(TG_E_STATE, "tg_rollout_mlp: no parameters (tg_policy_mlp_load)");
+  if (h->mode == TG_MODE_FLOW)
+    return fail(TG_E_INVAL, "tg_rollout_mlp: TG_MODE_FLOW evaluates its policy inside k_flow; use "
+                            "TG_MODE_COMPACT or TG_MODE_DIRECT");
+  if (steps == 0) return TG_OK;
+  if (steps < 0 || !reward || !valid || !done || (mode != TG_MLP_SAMPLE && mode != TG_MLP_GREEDY))
+    return fail(TG_E_INVAL, "tg_rollout_mlp: bad arguments");
+  const int64_t n = h->n;
+  if (!obs && !h->obs_scratch)  // the step kernels always write an obs row
+    if (hipMalloc((void**)&h->obs_scratch, sizeof(double) * 9 * (size_t)n) != hipSuccess)
+      return fail(TG_E_NOMEM, "tg_rollout_mlp: obs scratch");
+  if (!actions && !h->mlp_actions)  // and always read an action row
+    if (hipMalloc((void**)&h->mlp_actions, sizeof(int32_t) * (size_t)n) != hipSuccess)
+      return fail(TG_E_NOMEM, "tg_rollout_mlp: action scratch");
+  const bool ar = (flags & TG_STEP_AUTORESET) != 0;
+  hipStream_t cs = (hipStream_t)stream;
+  const uint32_t tb = h->tstep;
+  h->tstep += (uint32_t)steps;
+  // step s of a stepper: the actor into row s, then the step kernels with those actions given
+  auto step_of = [&](StepCtx& c, int32_t s, hipStream_t st, hipEvent_t mid) {
+    int32_t* const act = actions ? actions + (size_t)s * n : h->mlp_actions;
+    const int rc = launch_policy_mlp(h, c.off, c.n, a0, t0 + s, mode, act,
+                                     logp ? logp + (size_t)s * n : nullptr,
+                                     value ? value + (size_t)s * n : nullptr, nullptr, st);
+    if (rc) return rc;
+    const StepIO io{act, obs ? obs + (size_t)s * n * 9 : h->obs_scratch, reward + (size_t)s * n,
+                    valid + (size_t)s * n, done + (size_t)s * n, nullptr, -1, 0, 0};
+    return launch_step(h, c, io, ar, st, tb + (uint32_t)s, mid);
+  };
+  int rc = TG_OK;
+  if (h->grp.empty() || h->mode != TG_MODE_COMPACT) {
+    for (int32_t s = 0; s < steps && !rc; ++s) rc = step_of(h->main, s, cs, nullptr);
+    return rc;
+  }
+  // groups, as tg_rollout: each on its own stream, forked from and joined to the caller's
+  if ((rc = launch_regen(h, h->main, cs))) return rc;
+  HIP_TRY(hipEventRecord(h->fork, cs));
+  for (auto& c : h->grp) HIP_TRY(hipStreamWaitEvent(c.st, h->fork, 0));
+  for (int32_t s = 0; s < steps; ++s)
+    for (size_t g = 0; g < h->grp.size(); ++g) {
+      StepCtx& c = h->grp[g];
+      hipEvent_t mid = (s == 0 && h->stagger && g + 1 < h->grp.size()) ? h->grp[g + 1].ev : nullptr;
+      if ((rc = step_of(c, s, c.st, mid))) return rc;
       if (mid) HIP_TRY(hipStreamWaitEvent(h->grp[g + 1].st, mid, 0));
     }
   for (auto& c : h->grp) {

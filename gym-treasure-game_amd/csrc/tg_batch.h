@@ -144,6 +144,11 @@ struct tg_batch {
   int64_t regen_timed = 0;
   std::string domain;              // domain.txt text (the renderer's cell sprites)
   double* obs_scratch = nullptr;   // tg_rollout without an obs output
+  // the learned actor (tg_policy_mlp_load): its packed parameters (sized for the widest network
+  // at the first load and never reallocated), hidden width (0: none loaded), TG_ACT_*, masking
+  float* mlp_params = nullptr;
+  int mlp_hidden = 0, mlp_act = 0, mlp_masked = 0;
+  int32_t* mlp_actions = nullptr;  // tg_rollout_mlp without an actions output
   tg::TgOne* one = nullptr;            // tg_step1's row: pinned host memory the kernel writes
   tg::TgOne* one_dev = nullptr;        //   (its device-side address)
   uint16_t* mask1 = nullptr;           // tg_available_mask1's answer without the server (pinned)

@@ -106,6 +106,67 @@ def _ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+# ---- the learned actor's parameters (tg_policy_mlp_load; include/tg_amd.h) -------------------
+MLP_HIDDEN = (16, 32, 64, 128)
+MLP_KEYS = ("obs_scale", "obs_shift", "w1", "b1", "w2", "b2", "wp", "bp", "wv", "bv")
+
+
+def mlp_param_count(hidden):
+    """Packed f32 values of a network of hidden width ``hidden``: H*H + 21*H + 28."""
+    h = int(hidden)
+    if h not in MLP_HIDDEN:
+        raise ValueError("hidden must be one of %s (got %r)" % (MLP_HIDDEN, hidden))
+    return h * h + 21 * h + 28
+
+
+def _mlp_hidden_of(count):
+    for h in MLP_HIDDEN:
+        if mlp_param_count(h) == count:
+            return h
+    raise ValueError("%d values are no packed parameter array (H*H + 21*H + 28 for H in %s)"
+                     % (count, MLP_HIDDEN))
+
+
+def pack_mlp_params(params):
+    """The actor's parameters as the one flat float32 array tg_policy_mlp_load reads:
+    obs_scale[9], obs_shift[9], W1[H][9], b1[H], W2[H][H], b2[H], Wp[9][H], bp[9], Wv[H], bv[1].
+
+    ``params``: a dict of arrays or tensors with the keys ``obs_scale, obs_shift, w1, b1, w2, b2,
+    wp, bp, wv, bv``; the weights in torch's ``nn.Linear.weight`` orientation [out, in] (``wv``
+    [H] or [1, H], ``bv`` a scalar or [1]).  Shapes are checked (``ValueError``).  Needs no GPU."""
+    a = {}
+    for k in MLP_KEYS:
+        if k not in params:
+            continue
+        v = params[k]
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu().numpy()
+        a[k] = np.asarray(v, dtype=np.float32)
+    _mlp_check_shapes(a)
+    return np.concatenate([a[k].reshape(-1) for k in MLP_KEYS]).astype(np.float32)
+
+
+def _mlp_check_shapes(a):
+    """ValueError unless the dict holds every key with its shape; returns H"""
+    missing = [k for k in MLP_KEYS if k not in a]
+    if missing:
+        raise ValueError("params lacks %s" % ", ".join(missing))
+    w2 = tuple(a["w2"].shape)
+    if len(w2) != 2 or w2[0] != w2[1]:
+        raise ValueError("w2 must be [H, H] (got %s)" % (w2,))
+    h = w2[0]
+    if h not in MLP_HIDDEN:
+        raise ValueError("hidden width %d: must be one of %s" % (h, MLP_HIDDEN))
+    shapes = {"obs_scale": [(9,)], "obs_shift": [(9,)], "w1": [(h, 9)], "b1": [(h,)],
+              "w2": [(h, h)], "b2": [(h,)], "wp": [(9, h)], "bp": [(9,)],
+              "wv": [(h,), (1, h)], "bv": [(), (1,)]}
+    for k in MLP_KEYS:
+        if tuple(a[k].shape) not in shapes[k]:
+            raise ValueError("%s has shape %s, expected %s (H = %d)"
+                             % (k, tuple(a[k].shape), " or ".join(map(str, shapes[k])), h))
+    return h
+
+
 class TreasureGameVec:
     """``num_envs`` Treasure Game envs resident in one GPU's HBM.
 
@@ -222,11 +283,14 @@ class TreasureGameVec:
         [K, N], and (optionally) obs f64 [K, N, 9], actions i32 [K, N].  With auto-reset the
         obs rows are the post-reset ones and finished episodes queue for ``episodes()``.
 
+        ``policy="mlp"`` / ``"mlp_greedy"``: the learned actor of ``set_policy_mlp`` instead
+        (tg_rollout_mlp: per step the actor kernel, then the step kernels), which also returns
+        "logp" and "value" f32 [K, N]; not in "flow" mode.
+
         In "flow" mode a k_flow launch that fails its protocol checks (a wait past its bound,
         a sub-problem left unstepped, an item out of range) sets TG_ERR_FLOW and its rows are
         not valid: with ``check_flow`` (the default) the call then synchronises on
         ``errors()`` and raises TgError."""
-        pol = {"uniform": _lib.TG_POLICY_UNIFORM, "masked": _lib.TG_POLICY_MASKED}[policy]
         k, n, dev = int(steps), self.num_envs, self.device
         out = {"reward": torch.empty((k, n), dtype=torch.int32, device=dev),
                "valid": torch.empty((k, n), dtype=torch.uint8, device=dev),
@@ -235,6 +299,22 @@ class TreasureGameVec:
             out["obs"] = torch.empty((k, n, 9), dtype=torch.float64, device=dev)
         if actions:
             out["actions"] = torch.empty((k, n), dtype=torch.int32, device=dev)
+        if policy in ("mlp", "mlp_greedy"):
+            # the learned actor (set_policy_mlp) as the policy: also "logp" and "value" f32 [K, N];
+            # the row the policy saw at step s is obs[s - 1] (observe() before the call for s = 0)
+            if self._mode == "flow":
+                raise TgError("rollout(policy=%r) needs the compact or direct mode (k_flow "
+                              "evaluates its policy inside the kernel)" % policy)
+            out["logp"] = torch.empty((k, n), dtype=torch.float32, device=dev)
+            out["value"] = torch.empty((k, n), dtype=torch.float32, device=dev)
+            check(self._L.tg_rollout_mlp(
+                self.handle, k, action_seed, int(t0),
+                _lib.TG_MLP_GREEDY if policy == "mlp_greedy" else _lib.TG_MLP_SAMPLE,
+                _lib.TG_STEP_AUTORESET if self.autoreset else 0, _ptr(out.get("actions")),
+                _ptr(out.get("obs")), _ptr(out["reward"]), _ptr(out["valid"]), _ptr(out["done"]),
+                _ptr(out["logp"]), _ptr(out["value"]), self._stream()), "tg_rollout_mlp")
+            return out
+        pol = {"uniform": _lib.TG_POLICY_UNIFORM, "masked": _lib.TG_POLICY_MASKED}[policy]
         check(self._L.tg_rollout(self.handle, k, action_seed, int(t0), pol,
                                  _lib.TG_STEP_AUTORESET if self.autoreset else 0,
                                  _ptr(out.get("actions")), _ptr(out.get("obs")),
@@ -270,6 +350,66 @@ class TreasureGameVec:
         check(self._L.tg_policy_actions(self.handle, action_seed, int(t), pol, _ptr(out),
                                         self._stream()), "tg_policy_actions")
         return out
+
+    def set_policy_mlp(self, params, act="tanh", masked=True):
+        """Load the learned actor (tg_policy_mlp_load): a two-hidden-layer MLP over the obs row
+        with a 9-way policy head and a value head (the arithmetic: include/tg_amd.h).
+
+        ``params``: the dict ``pack_mlp_params`` takes, or an already packed float32 array /
+        tensor (a device tensor is used in place).  The copy into the handle's buffer is
+        queued on the current stream, so weights can be refreshed between rollouts without a
+        synchronisation.  ``masked``: sample among the options ``available_mask`` allows."""
+        a = {"relu": _lib.TG_ACT_RELU, "tanh": _lib.TG_ACT_TANH}[act]
+        if isinstance(params, dict):
+            if all(isinstance(v, torch.Tensor) and v.device == self.device
+                   for v in params.values()):  # a module's tensors: packed on the device
+                _mlp_check_shapes(params)
+                params = torch.cat([params[k].detach().reshape(-1).to(torch.float32)
+                                    for k in MLP_KEYS])
+            else:
+                params = pack_mlp_params(params)
+        p = torch.as_tensor(params)
+        if p.dtype != torch.float32 or p.dim() != 1:
+            raise ValueError("packed parameters must be a flat float32 array")
+        hidden = _mlp_hidden_of(p.numel())
+        p = p.to(self.device).contiguous()
+        check(self._L.tg_policy_mlp_load(self.handle, hidden, a, 1 if masked else 0, _ptr(p),
+                                         self._stream()), "tg_policy_mlp_load")
+        self.mlp_hidden = hidden
+
+    def policy_mlp(self, t, action_seed=0x5EED0001, greedy=False, logits=False, out=None):
+        """The learned actor on every env's current state for step ``t`` (tg_policy_mlp):
+        ``(actions i32 [N], logp f32 [N], value f32 [N])`` and, with ``logits``, the policy
+        head's f32 [N, 9].  Sampling is keyed by (action_seed, GLOBAL env id, t); ``greedy``
+        takes the allowed argmax.  The tensors are the env's own buffers, overwritten by the
+        next call, unless ``out`` gives some ({"actions", "logp", "value", "logits"}: contiguous
+        device tensors of exactly those shapes and dtypes)."""
+        n, dev = self.num_envs, self.device
+        want = {"actions": ((n,), torch.int32), "logp": ((n,), torch.float32),
+                "value": ((n,), torch.float32), "logits": ((n, 9), torch.float32)}
+        bufs = {}
+        for k, (shape, dt) in want.items():
+            if k == "logits" and not logits:
+                continue
+            b = None if out is None else out.get(k)
+            if b is None:
+                own = getattr(self, "_mlp_out", None)
+                if own is None:
+                    own = self._mlp_out = {}
+                if k not in own:
+                    own[k] = torch.empty(shape, dtype=dt, device=dev)
+                b = own[k]
+            elif not (isinstance(b, torch.Tensor) and b.dtype == dt and tuple(b.shape) == shape
+                      and b.is_contiguous() and b.device == dev):
+                raise ValueError("out[%r] must be a contiguous %s tensor of shape %s on %s"
+                                 % (k, dt, shape, dev))
+            bufs[k] = b
+        check(self._L.tg_policy_mlp(self.handle, action_seed, int(t),
+                                    _lib.TG_MLP_GREEDY if greedy else _lib.TG_MLP_SAMPLE,
+                                    _ptr(bufs["actions"]), _ptr(bufs["logp"]), _ptr(bufs["value"]),
+                                    _ptr(bufs.get("logits")), self._stream()), "tg_policy_mlp")
+        res = (bufs["actions"], bufs["logp"], bufs["value"])
+        return res + (bufs["logits"],) if logits else res
 
     def drain_episodes(self, out, count):
         """Asynchronous device drain: up to out.shape[0] records -> ``out`` (int64 [cap, 2],

@@ -354,6 +354,56 @@ int tg_frame_shape_scaled(const tg_batch *h, int32_t scale, int32_t *height, int
 int tg_render_scaled(tg_batch *h, int64_t first, int64_t count, int32_t scale, int32_t channels,
                      uint8_t *out, void *stream);
 
+/* ---- a learned actor on the device (an extension: the reference has no policy) -------------
+ * A two-hidden-layer MLP over the 9-dimensional observation with a 9-way policy head and a
+ * value head.  Hidden width H is 16, 32, 64 or 128; the activation is TG_ACT_RELU or
+ * TG_ACT_TANH.  The parameters are one packed f32 array of H*H + 21*H + 28 values:
+ *   obs_scale[9], obs_shift[9], W1[H][9], b1[H], W2[H][H], b2[H], Wp[9][H], bp[9], Wv[H], bv[1]
+ * Arithmetic: all f32, every multiply-add an explicit fmaf (the build has -ffp-contract=off).
+ * With chain(c; w, x): for k ascending, c = fmaf(w[k], x[k], c), and o[9] the env's observation
+ * (exactly the f64 row tg_observe writes):
+ *   x[j]     = fmaf((float)o[j], obs_scale[j], obs_shift[j])
+ *   a1[i]    = act(chain(b1[i]; W1[i], x))
+ *   a2[i]    = act(chain(b2[i]; W2[i], a1))
+ *   logit[k] = chain(bp[k]; Wp[k], a2)
+ *   value    = chain(bv; Wv, a2)
+ * relu is z > 0 ? z : 0, tanh is tanhf(z).  So logits and value do not depend on batch size,
+ * sharding or the kernel's tiling, and a ReLU network's are reproducible bit for bit on a CPU.
+ * Allowed set A: the set bits of the env's available_mask when `masked` is set and the mask is
+ * non-zero, else all 9 actions (TG_POLICY_MASKED's fallback).
+ * Sampling: m = max of logit[k] over A; e[k] = expf(logit[k] - m) for k in A; Z = the f32 sum of
+ * e[k] over A in ascending k; h = sm64(sm64(a0 ^ sm64(g)) ^ t) with g the GLOBAL env index
+ * (tg_policy_actions' hash); u = (float)(h >> 40) * 2^-24, thr = u * Z; the action is the first k
+ * in A, ascending, whose running f32 sum of e exceeds thr, else the last k in A.
+ * TG_MLP_GREEDY: the lowest k in A with logit[k] == m.  Both: logp = (logit[a] - m) - logf(Z).
+ * With non-finite parameters or activations the results are unspecified, but every index is
+ * derived from A, never from a float: nothing faults and a masked action is never chosen. */
+#define TG_ACT_RELU 0
+#define TG_ACT_TANH 1
+#define TG_MLP_SAMPLE 0
+#define TG_MLP_GREEDY 1
+/* Copies the packed parameters (a DEVICE pointer) on `stream` into a buffer the handle owns,
+ * device to device and asynchronously: a learner refreshes the weights between rollouts without
+ * a synchronisation, and calls queued earlier on the stream still see the earlier weights.  (The
+ * first load allocates that buffer.)  A bad hidden or act or a null pointer: TG_E_INVAL. */
+int tg_policy_mlp_load(tg_batch *h, int32_t hidden, int32_t act, int32_t masked,
+                       const float *params_dev, void *stream);
+/* The actor on the current state of every env for step t: actions int32 [N], and where not NULL
+ * logp f32 [N], value f32 [N], logits f32 [N][9].  mode: TG_MLP_*.  TG_E_STATE before a load. */
+int tg_policy_mlp(tg_batch *h, uint64_t action_seed, int64_t t, int32_t mode, int32_t *actions,
+                  float *logp, float *value, float *logits, void *stream);
+/* K steps in one call with the actor as the policy: step t0 + s runs the actor kernel into row s,
+ * then the step kernels with those actions given.  Step-major outputs as tg_rollout: actions
+ * (may be NULL) int32 [K][N], obs (may be NULL) f64 [K][N][9], reward, valid, done, and logp,
+ * value (each may be NULL) f32 [K][N].  Identical to K x (tg_policy_mlp + tg_step).  The row the
+ * policy saw at step s is obs[s - 1] (for s = 0: tg_observe before the call), also after an
+ * auto-reset: the row is then the new episode's first observation.  TG_MODE_COMPACT and
+ * TG_MODE_DIRECT; with tg_set_groups each group launches the actor for its own envs on its own
+ * stream.  TG_MODE_FLOW: TG_E_INVAL (k_flow evaluates its policy inside the kernel). */
+int tg_rollout_mlp(tg_batch *h, int32_t steps, uint64_t action_seed, int64_t t0, int32_t mode,
+                   uint32_t flags, int32_t *actions, double *obs, int32_t *reward, uint8_t *valid,
+                   uint8_t *done, float *logp, float *value, void *stream);
+
 const char *tg_last_error(void);
 const char *tg_version(void);
 
