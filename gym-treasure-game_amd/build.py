@@ -5,18 +5,16 @@
 The flags matter for parity: -ffp-contract=off keeps uniform()'s a + (b-a)*r and the obs
 divisions IEEE-exact (no FMA contraction), and fast-math is never enabled.
 """
+import glob
 import os
 import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRCS = [os.path.join(HERE, "csrc", f) for f in ("tg_amd.hip", "tg_render.hip")]
-# k_flow's own unit, compiled with FLOW_FLAGS and linked into the same library (tg_flow.hip)
-FLOW_SRC = os.path.join(HERE, "csrc", "tg_flow.hip")
+# k_flow's own unit (tg_flow.hip) is compiled with FLOW_FLAGS and linked into the same library
 FLOW_FLAGS = ["-mllvm", "-disable-machine-licm"]
-DEPS = SRCS + [FLOW_SRC] + [os.path.join(HERE, "csrc", f) for f in ("tg_core.h", "tg_level.h", "tg_batch.h",
-                                                        "tg_render.h", "tg_render_scaled.h", "tg_twist.h",
-                                                        "tg_flow.h", "tg_policy_mlp.h")] + [
+# every source and header of csrc/ (a new header is a dependency without being named here)
+DEPS = sorted(glob.glob(os.path.join(HERE, "csrc", "*.hip")) + glob.glob(os.path.join(HERE, "csrc", "*.h"))) + [
     os.path.join(os.path.dirname(HERE), "include", "tg_amd.h")]
 OUT = os.path.join(HERE, "libtg_amd.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -1,5 +1,6 @@
-// tg_batch.h — the handle behind include/tg_amd.h, shared by the step (tg_amd.hip) and render
-// (tg_render.hip) translation units of libtg_amd.so.  Internal: not part of the C ABI.
+// tg_batch.h — the handle behind include/tg_amd.h, shared by the step (tg_amd.hip; tg_flow.hip
+// through tg_dev.h, for Soa) and render (tg_render.hip) translation units of libtg_amd.so.
+// Internal: not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -46,7 +47,7 @@ struct TgOne {
 };
 static_assert(sizeof(TgOne) == 80, "TgOne: ten 8-B words (k_serve1 copies it out by word)");
 
-// The N = 1 server's mailbox (k_serve1, tg_amd.hip): pinned, coherent host memory (line 2:
+// The N = 1 server's mailbox (k_serve1, tg_py1.h): pinned, coherent host memory (line 2:
 // TG_SERVE_TRACE's stamps).  Line 0 is
 // the host's: a command is one 16-B group (seq last: the server reads the group with one load,
 // and a group whose seq is new carries the command's fields) and, for a reset, gauss_next

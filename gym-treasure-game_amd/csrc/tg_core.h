@@ -1,7 +1,7 @@
 // tg_core.h — per-env Treasure Game step physics for the MI355X kernel (gfx950).
 //
 // Everything here is `__host__ __device__` integer code operating on one env held in
-// registers.  tg_amd.hip wraps it in the batched kernels (one wavefront lane per env, level
+// registers.  tg_dev.h and tg_kernels.h wrap it in the batched kernels (one wavefront lane per env, level
 // grid in LDS, struct-of-arrays state in HBM).  The host instantiation exists only so the
 // test harness (tests/native/) can run the exact same code on the build machine, which has
 // no GPU; the product API never executes it on the CPU.
@@ -39,7 +39,7 @@ constexpr int TICK_CAP = 1 << 14;  // the reference has no cap (OP/:28-31); obse
 // cascade can change one handle several times.  Its bound depends on the level's trigger
 // table: Level::interact_draws (tg_level.h interact_draw_bound), at most MAX_TICK_DRAWS.
 constexpr uint32_t TICK_DRAWS = 8;
-constexpr uint32_t MAX_TICK_DRAWS = 48;  // what a refilled code window always holds (tg_amd.hip)
+constexpr uint32_t MAX_TICK_DRAWS = 48;  // what a refilled code window always holds (tg_dev.h)
 constexpr int PAD = 2;         // WALL cells around the grid in LDS (probes reach <= 60 px out)
 
 // Cell bits in the LDS grid.  A door object's cell carries only its one-hot door bit: its type
@@ -136,7 +136,7 @@ TG_HD int floordiv48(int a) { return div48(a + 16 * S) - 16; }              // -
 //   regenerated: MT_HALF_GENS twists in sequence from the last generation of the half the
 //   lane is in (twist_half); the env's state word carries MT_STALE meanwhile.  The kernels
 //   regenerate it later, a whole wavefront per env, coalesced, the chained twists in LDS
-//   (tg_amd.hip twist_chain: k_regen every 16 steps, k_reset, k_step).  A launch that
+//   (tg_twist.h twist_chain: k_regen every 16 steps, k_reset, k_step).  A launch that
 //   would enter a stale half (> MT_HALF draws since the refill) regenerates it first, per
 //   lane.  Seeding (init_by_array) fills the ring's last generation; 2 x MT_HALF_GENS twists
 //   then give generations 1 .. 2 x MT_HALF_GENS, pos 0 (init_mt).
@@ -198,7 +198,7 @@ TG_HD void twist_gen_inplace(uint32_t* w) { twist_gen(w, w); }
 // new word j0 = i - 227 d (< 227, which reads old words only).  The chain's old words are at
 // fixed offsets from j0 and all load unconditionally (indices clamped into the generation):
 // one memory round trip, and no divergence between lanes of different chain lengths.
-// (Ld: how a stored word is read — plain, or k_flow's L1-bypassing load, tg_amd.hip)
+// (Ld: how a stored word is read — plain, or k_flow's L1-bypassing load, tg_dev.h)
 struct PlainLd {
   TG_HD uint32_t operator()(const uint32_t* p) const { return *p; }
 };
@@ -344,7 +344,7 @@ TG_HD void gen_codes(const uint32_t* words, uint8_t* c) {
 // each odd generation goes to the next slot and becomes the even one after it in place;
 // generation 7 (codes only) is twisted in place over generation 6, which is then made again
 // from generation 4 (two extra twists on this rare per-lane path, no other scratch).
-// (Ops: the whole-generation loops, inline here; tg_amd.hip's regen_half calls them out of line
+// (Ops: the whole-generation loops, inline here; tg_dev.h's regen_half calls them out of line
 // so that k_run's register allocation does not grow around its rare call)
 struct GenOps {
   TG_HD void twist(const uint32_t* src, uint32_t* dst) const { twist_gen(src, dst); }
@@ -423,7 +423,7 @@ struct Rng {
   TG_HD void reserve(uint32_t) {}
   TG_HD bool has(uint32_t) const { return true; }
   TG_HD bool overrun() const { return false; }
-  TG_HD void phase(int) {}  // per-phase timing hook of the diagnostic build (tg_amd.hip RngCodes)
+  TG_HD void phase(int) {}  // per-phase timing hook of the diagnostic build (tg_dev.h RngCodes)
   template <int DIR>
   TG_HD int walk(int& x, int lim, int cap) { return walk_ticks<DIR>(*this, x, lim, cap); }
   // the state word to store: position, and whether the other half is stale

@@ -1,0 +1,776 @@
+// tg_dev.h — the device layer both device units of the step code compile: tg_amd.hip (the per-step
+// kernels of tg_kernels.h and tg_py1.h) and tg_flow.hip (k_flow, tg_flow.h).  __device__
+// functions, types and constants only: no kernel and no host code, so an edit here changes both
+// units and an edit anywhere else changes one.
+//
+// One wavefront lane per env.  Per launch every lane loads its env from struct-of-arrays
+// HBM (16-B + 16-B + 8-B coalesced loads), runs the requested option to completion
+// (_Option.run, OP/:20-36) over the level grid staged in LDS, writes obs / reward / valid /
+// done, and stores the env back.  Auto-reset compacts completed episodes with a wavefront
+// ballot + one atomic per wave.  No MFMA: the path is integer/branch work plus a handful of
+// IEEE f64 ops (obs divisions, uniform/gauss), built with -ffp-contract=off.
+//
+// HBM layout per handle (N envs):
+//   st4[N]  uint4   {pos = px | py<<16 (i16 pair), flags, objs = kx,ky,gx,gy (i8 x4), mt_pos}
+//   ang[N]  double2 {handle0.angle, handle1.angle}
+//   ep[N]   int2    {episode return, episode length}
+//   mt[N][624] u32  env-major MT19937 words (2,496 B per env)
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/tg_amd.h"
+#include "tg_core.h"
+#include "tg_level.h"
+#include "tg_batch.h"
+#include "tg_twist.h"
+
+using namespace tg;
+
+namespace {
+
+constexpr int BLOCK = 256;
+// k_run's workgroup: a workgroup holds its CU slot (LDS, wave slots) until its slowest wave
+// ends, and k_run's waves differ in length by up to ~3x
+#ifndef TG_RUN_BLOCK
+#define TG_RUN_BLOCK 256
+#endif
+constexpr int RUN_BLOCK = TG_RUN_BLOCK;
+static_assert(RUN_BLOCK % 64 == 0 && BLOCK % RUN_BLOCK == 0, "whole waves, whole k_classify blocks");
+// issue priority of the option waves whose ticks are slow (ladders, drops, jumps), which share
+// SIMDs with the go waves (0.153 vs 0.156 ms per step)
+constexpr int PRIO_SLOW = 3;
+
+// ------------------------------------------------------------------------------------------
+// SoA pack / unpack
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ void unpack_st4(const uint4 s, Env& e) {
+  e.px = (int)(int16_t)(s.x & 0xFFFFu);
+  e.py = (int)(int16_t)(s.x >> 16);
+  e.f = s.y;
+  e.kx = (int)(int8_t)(s.z & 0xFF);
+  e.ky = (int)(int8_t)((s.z >> 8) & 0xFF);
+  e.gx = (int)(int8_t)((s.z >> 16) & 0xFF);
+  e.gy = (int)(int8_t)(s.z >> 24);
+  e.mti = s.w;
+}
+__device__ __forceinline__ void unpack(const uint4 s, const double2 a, Env& e) {
+  unpack_st4(s, e);
+  e.ang0 = a.x;
+  e.ang1 = a.y;
+}
+__device__ __forceinline__ uint4 pack(const Env& e) {
+  uint4 s;
+  s.x = ((uint32_t)e.px & 0xFFFFu) | ((uint32_t)e.py << 16);
+  s.y = e.f;
+  s.z = ((uint32_t)e.kx & 0xFF) | (((uint32_t)e.ky & 0xFF) << 8) | (((uint32_t)e.gx & 0xFF) << 16) |
+        ((uint32_t)e.gy << 24);
+  s.w = e.mti;
+  return s;
+}
+
+// The level in LDS: the bordered cell grid (per-lane indexed probes) and the trigger table
+// (indexed per lane by the cascade; kernel arguments indexed per lane would be vector loads
+// from the kernarg segment).
+struct LdsLevel {
+  uint32_t trig[12];
+  uint32_t grid[MAX_CELLS / 4];
+};
+TG_HD int grid_words(int W, int H) { return ((W + 2 * PAD) * (H + 2 * PAD) + 3) / 4; }
+// grid words, trigger table and (masks: non-null) the level bitmasks into LDS; NT: the
+// workgroup's threads
+template <int NT = BLOCK>
+__device__ __forceinline__ void stage_cells(uint32_t* lgrid, uint32_t* ltrig,
+                                            const uint32_t* __restrict__ grid, const Level& L,
+                                            uint32_t* masks = nullptr) {
+  const int nwords = grid_words(L.W, L.H);
+  for (int i = threadIdx.x; i < nwords; i += NT) lgrid[i] = grid[i];
+  if (threadIdx.x < 12) ltrig[threadIdx.x] = L.trig[threadIdx.x >> 1][threadIdx.x & 1];
+  if (masks && L.masks)
+    for (int i = threadIdx.x; i < mk_words(L.W, L.H); i += NT) masks[i] = L.masks[i];
+  __syncthreads();
+}
+__device__ __forceinline__ void stage_level(LdsLevel& lv, const uint32_t* __restrict__ grid,
+                                            const Level& L) {
+  stage_cells(lv.grid, lv.trig, grid, L);
+}
+#define LEVEL_IN_LDS()                   \
+  __shared__ LdsLevel lv;                \
+  stage_level(lv, grid, L);              \
+  const uint32_t* const trig = lv.trig;  \
+  const Map m{reinterpret_cast<const uint8_t*>(lv.grid), L.W, L.H}
+// k_run's LDS: the waves' code windows (WIN_WAVE_BYTES each, at offset 0: 16-B aligned for the
+// LDS-DMA), then the level's grid words and bitmasks (Map::mk).  (Sized at launch for the
+// handle's level instead of the largest, with the rows' loads issued before the staging
+// barrier, it measured ~4 % slower for the masked policy: DESIGN.md §3.1.)
+#define RUN_LEVEL_IN_LDS()                                                                \
+  __shared__ uint4 run_lds[((RUN_BLOCK / 64) * WIN_WAVE_BYTES + MAX_CELLS + 4 * MK_MAX_WORDS) / 16]; \
+  __shared__ uint32_t ltrig[12];                                                          \
+  uint8_t* const win = reinterpret_cast<uint8_t*>(run_lds);                                \
+  uint32_t* const lgrid = reinterpret_cast<uint32_t*>(win + (RUN_BLOCK / 64) * WIN_WAVE_BYTES); \
+  uint32_t* const lmk = lgrid + grid_words(L.W, L.H);                                     \
+  stage_cells<RUN_BLOCK>(lgrid, ltrig, grid, L, lmk);                                     \
+  const uint32_t* const trig = ltrig;                                                     \
+  const Map m{reinterpret_cast<const uint8_t*>(lgrid), L.W, L.H, L.masks ? lmk : nullptr}
+
+__device__ __forceinline__ void store_obs(double* out, int64_t i, const double o[9]) {
+  double* p = out + i * 9;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) p[k] = o[k];
+}
+
+// ------------------------------------------------------------------------------------------
+// CPython random for the option loops (k_run, k_step): tg::Rng's read-only consumption of the
+// two pre-twisted generations, reading each draw's code byte (tg_core.h draw_code: its noisy /
+// jump / flip outcomes) from a per-lane window in LDS.
+//   Window: WIN_CHUNKS 16-B chunks (16 codes each) per lane, slot j of the wave's window at
+//   m0 + j * 1 KB holding the lane's j-th chunk from where the window starts.  prime() fills
+//   it with one LDS-DMA (global_load_lds_dwordx4) per slot: every lane's chunk j goes to slot
+//   j, so M0 (which addresses the DMA's LDS destination and must be wave-uniform) is the same
+//   for all of them and each slot costs ONE instruction.  The first draw waits for the DMAs
+//   (s_waitcnt vmcnt(0), once per launch; k_run primes before the option's setup so the wait
+//   is mostly covered); every later draw is an LDS byte read, issued one draw ahead.  The
+//   window holds 112 draws, more than an option of the default level consumes in one step
+//   (<= ~110); a lane that exhausts it refills it the same way (WAR: lgkmcnt(0) before the
+//   DMAs; RAW: vmcnt(0) after) and pays one memory latency.  The DMAs are issued from inline
+//   asm, invisible to the compiler's waitcnt pass, so no register copy of a loaded value is
+//   waited for early (a register-held prefetch made the compiler wait at the load).
+//   Position bookkeeping is deferred: the window start (pos) plus the draws taken since (n)
+//   are folded into pos at a refill and at finish.
+//   Stale halves: a window overlapping the half the lane is not in, while that half is stale
+//   (crossed), is loaded only after the lane has regenerated that half itself (regen_half:
+//   rare, > 312 draws since the refill; the refilling idle wave, if any, writes the same).
+//   Draws that need the double (handle angles in a flip cascade, an auto-reset's uniform and
+//   gauss) consume the code and read the position's two words (one 8-B load).
+// ------------------------------------------------------------------------------------------
+// code bytes per lane per LDS-DMA (global_load_lds_dwordx4).  The dword form (lane l's 4 B at
+// M0 + 4l, no LDS bank conflicts) needs 4x the DMA instructions per fill and measured 7 %
+// slower (profiles/r03/lds_window_ab.json)
+constexpr int WIN_UNIT = 16;
+constexpr int WIN_DRAWS = 64;                       // codes per lane in the window
+constexpr int WIN_SLOTS = WIN_DRAWS / WIN_UNIT;     // DMA instructions per fill
+constexpr int WIN_SLOT_BYTES = 64 * WIN_UNIT;       // one slot: every lane's unit
+constexpr uint32_t CODE_UNITS = MT_CODES / WIN_UNIT;
+static_assert(MT_CODES % WIN_UNIT == 0, "whole DMA units of codes per env");
+constexpr int WIN_WAVE_BYTES = WIN_SLOTS * WIN_SLOT_BYTES;  // 4 KB per wave
+constexpr int WAVE_SCRATCH = MT_N * 4;                       // wave_twist's scratch (aliases it)
+static_assert(WIN_WAVE_BYTES >= WAVE_SCRATCH, "wave_refill reuses the window as scratch");
+static_assert(WIN_DRAWS - WIN_UNIT + 1 >= (int)MAX_TICK_DRAWS, "a refilled window holds a tick's draws");
+
+// LDS-DMA of one WIN_UNIT-byte unit per active lane into LDS [m0 + lane * WIN_UNIT]; M0 is
+// saved/restored.  SC1: the load bypasses this CU's L1 (k_flow, whose codes another CU of the
+// XCD may have rewritten in the same launch: tg_flow.h)
+template <bool SC1 = false>
+__device__ __forceinline__ void glds_unit(uint32_t m0, const void* gptr) {
+  uint32_t save;
+  if constexpr (SC1)
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %1\n\t"
+        "s_nop 0\n\t"
+        "global_load_lds_dwordx4 %2, off sc1\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(save)
+        : "s"(__builtin_amdgcn_readfirstlane(m0)), "v"(gptr)
+        : "memory");
+  else
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %1\n\t"
+        "s_nop 0\n\t"
+        "global_load_lds_dwordx4 %2, off\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(save)
+        : "s"(__builtin_amdgcn_readfirstlane(m0)), "v"(gptr)
+        : "memory");
+}
+
+// the rare second crossing (RngCodes::fill), out of line so that the draw sites stay small, its
+// generation loops out of line too: a callee's registers add to its caller's allocation (k_run
+// 104 VGPRs, 4 waves per SIMD, with them inline)
+__device__ __noinline__ void twist_gen_call(const uint32_t* src, uint32_t* dst) { twist_gen(src, dst); }
+__device__ __noinline__ void gen_codes_call(const uint32_t* w, uint8_t* c) { gen_codes(w, c); }
+struct GenCalls {
+  __device__ void twist(const uint32_t* src, uint32_t* dst) const { twist_gen_call(src, dst); }
+  __device__ void codes(const uint32_t* w, uint8_t* c) const { gen_codes_call(w, c); }
+};
+__device__ __noinline__ void regen_half(uint32_t* mt, uint8_t* mc, uint32_t h) {
+  twist_half(mt, h, mc, false, GenCalls());
+  asm volatile("s_waitcnt vmcnt(0)\n\tbuffer_inv sc0" ::: "memory");
+}
+// k_flow's form: the half's source words may have been written by another CU of the XCD in the
+// same launch (the env's previous item ran there), so this CU's L1 is invalidated first; the
+// stores go through the L1 (write-through) to the XCD's L2, where the env's next item, on
+// whichever CU of the XCD, reads them with L1-bypassing loads (tg_flow.h) once this wave's
+// stores are complete.  No L2 writeback: nothing crosses XCDs (an agent-scope release's
+// buffer_wbl2 here wrote back the XCD's whole L2 on every per-lane regeneration).
+__device__ __noinline__ void regen_half_flow(uint32_t* mt, uint8_t* mc, uint32_t h) {
+  asm volatile("buffer_inv sc1\n\ts_waitcnt vmcnt(0)" ::: "memory");
+  twist_half(mt, h, mc, false, GenCalls());
+  asm volatile("s_waitcnt vmcnt(0)\n\tbuffer_inv sc1\n\ts_waitcnt vmcnt(0)" ::: "memory");
+}
+
+// a stored MT word read past this CU's L1 (an agent-scope relaxed load: global_load sc1), for
+// k_flow, where another CU of the XCD may have rewritten it in the same launch (tg_flow.h)
+struct Sc1Ld {
+  __device__ uint32_t operator()(const uint32_t* p) const {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+};
+__device__ __noinline__ WordPair mt_pair_ool_sc1(const uint32_t* mt, uint32_t p) {
+  WordPair r;
+  mt_pair(mt, p, r.w0, r.w1, Sc1Ld());
+  return r;
+}
+
+template <bool FLOW = false>  // FLOW: k_flow's L1-bypassing loads (tg_flow.h)
+struct RngCodesT {
+  static constexpr uint32_t NONE = 0xFFFFFFFFu;
+  uint32_t* mt;      // this env's MT_STORE stored words (HBM)
+  uint8_t* mc;       // this env's MT_CODES code bytes (HBM)
+  lds_u8* cell;      // this lane's unit in slot 0 of the wave's window
+  uint32_t m0;       // LDS address of slot 0 of the wave's window (wave-uniform)
+  uint32_t pos;      // word position of the window's first draw (even)
+  uint32_t n;        // draws taken since then
+  uint32_t rd;       // LDS offset of the next draw's code from cell: slot * 1 KB + byte
+  uint32_t left;     // draws left in the window
+  uint32_t nxc;      // the next draw's code (read one draw ahead)
+  uint32_t stale;    // word offset (0 / 624) of the half that is two generations behind, or NONE
+  uint32_t tag;      // the state word's MT_STALE | MT_LISTED bits on entry
+  uint32_t draws;
+  uint32_t regens;   // halves this lane regenerated itself (regen_half)
+  bool primed, loaded, entered;  // entered: a half was entered in this launch (as tg::Rng)
+
+  __device__ __forceinline__ RngCodesT(uint32_t* m, uint8_t* c, uint32_t state, lds_u8* wave_win)
+      : mt(m), mc(c), cell(wave_win + (threadIdx.x & 63) * WIN_UNIT),
+        m0(__builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)wave_win)),
+        pos(state & MT_POS_MASK), n(0u), rd(0u), left(0u), nxc(0u),
+        stale((state & MT_STALE) ? (uint32_t)MT_HALF - mt_half(state & MT_POS_MASK) : NONE),
+        tag(state & (MT_STALE | MT_LISTED)),
+        draws(0u), regens(0u), primed(false), loaded(false), entered(false) {}
+
+  // fold the draws taken since the window start into pos (a window is < MT_HALF / 2 draws, so
+  // at most one half boundary lies in between).  Entering a half that is stale (possible only
+  // when the window ended exactly at the boundary, so nothing of it was read) regenerates it
+  // first, from the half being left, which then becomes the stale one.
+  __device__ __forceinline__ void sync() {
+    const uint32_t d = pos >> 1, e = d + n;
+    if (e / (MT_HALF / 2) != d / (MT_HALF / 2)) {
+      const uint32_t left_half = mt_half(pos), entered_half = (uint32_t)MT_HALF - left_half;
+      if (stale == entered_half) {
+        if (FLOW) regen_half_flow(mt, mc, entered_half);
+        else regen_half(mt, mc, entered_half);
+        ++regens;
+      }
+      stale = left_half;
+      entered = true;
+    }
+    pos = 2u * (e >= (uint32_t)MT_CODES ? e - (uint32_t)MT_CODES : e);
+    n = 0u;
+  }
+  // DMA the window starting at pos (all lanes reaching it start at slot 0: one DMA per slot)
+  __device__ __forceinline__ void fill() {
+    const uint32_t d = pos >> 1, c0 = d / (uint32_t)WIN_UNIT;
+    if (stale != NONE) {
+      // the draws the window serves are words [pos, pos + 2 * left) (mod MT_WORDS; the bytes of
+      // its first and last chunks outside that range are never read): regenerate the stale
+      // half first if they overlap it
+      const uint32_t w0 = pos, w1 = pos + 2u * ((uint32_t)WIN_DRAWS - d % (uint32_t)WIN_UNIT);
+      if ((w0 < stale + (uint32_t)MT_HALF && stale < w1) ||
+          (w1 > (uint32_t)MT_WORDS && stale < w1 - (uint32_t)MT_WORDS)) {
+        if (FLOW) regen_half_flow(mt, mc, stale);
+        else regen_half(mt, mc, stale);
+        ++regens;
+        stale = NONE;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < WIN_SLOTS; ++j) {
+      const uint32_t c = c0 + j < CODE_UNITS ? c0 + j : c0 + j - CODE_UNITS;
+      glds_unit<FLOW>(m0 + j * WIN_SLOT_BYTES, mc + c * (uint32_t)WIN_UNIT);
+    }
+    rd = d % (uint32_t)WIN_UNIT;
+    left = (uint32_t)WIN_DRAWS - rd;
+    loaded = false;
+  }
+  __device__ __forceinline__ uint32_t read() const {
+    const uint32_t r = rd < (uint32_t)WIN_DRAWS ? rd : 0u;  // stay inside the window
+    return cell[(r / WIN_UNIT) * WIN_SLOT_BYTES + r % WIN_UNIT];
+  }
+  __device__ __forceinline__ void prime() {
+    fill();
+    primed = true;
+  }
+  // at least k draws available in the window (the option loops call it once per tick: a tick
+  // draws at most 6 times; an auto-reset 4); refilling is rare and has one site per loop
+  __device__ __forceinline__ void reserve(uint32_t k) {
+    if (!primed) prime();
+    if (left < k) {
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // no read of the old window pending
+      sync();
+      fill();
+    }
+    if (!loaded) {  // the window's DMAs must have landed
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      nxc = read();
+      loaded = true;
+    }
+  }
+  // at least k draws staged (no refill: the plain go loop's exit test)
+  __device__ __forceinline__ bool has(uint32_t k) const { return left >= k; }
+  // the code dword holding draws 4d .. 4d + 3 of the window (d < WIN_DRAWS / 4)
+  __device__ __forceinline__ uint32_t dword(uint32_t d) const {
+    return *reinterpret_cast<const lds_u32*>(cell + (4u * d / WIN_UNIT) * WIN_SLOT_BYTES +
+                                             (4u * d) % WIN_UNIT);
+  }
+  // walk_ticks (tg_core.h) four draws per LDS read: the codes of a dword are applied one by one
+  // (each tick checks the span, the staged draws and the cap at its start, as walk_ticks), so
+  // the result is walk_ticks's; the next dword is read while this one is applied
+  template <int DIR>
+  __device__ __forceinline__ int walk(int& x, const int lim, const int cap) {
+    int taken = 0;
+    if (!((DIR > 0 ? x <= lim : x >= lim) && left >= TICK_DRAWS && cap > 0)) return 0;
+    uint32_t w = dword(rd >> 2);
+    while (true) {
+      const uint32_t wn = dword((rd >> 2) + 1u);  // inside the window: left >= TICK_DRAWS here
+      const int k = (int)(rd & 3u);
+      int moved = 0;
+      bool act = true;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int st = code_step((w >> (8 * i)) & 0xFFu, DIR < 0);
+        act = act && (i >= k ? ((DIR > 0 ? x <= lim : x >= lim) &&
+                                left - (uint32_t)moved >= TICK_DRAWS && taken + moved < cap)
+                             : true);
+        if (i >= k && act) {
+          x += st;
+          ++moved;
+        }
+      }
+      taken += moved;
+      rd += (uint32_t)moved;
+      left -= (uint32_t)moved;
+      n += (uint32_t)moved;
+      draws += (uint32_t)moved;
+      if (moved < 4 - k) break;  // the walk stopped inside this dword
+      if (!((DIR > 0 ? x <= lim : x >= lim) && left >= TICK_DRAWS && taken < cap)) break;
+      w = wn;
+    }
+    nxc = read();  // code() reads one draw ahead
+    return taken;
+  }
+#ifdef TG_DIAG_STAMPS
+  // DIAGNOSTIC BUILD ONLY: s_memtime per phase of the option loops (tg_core.h run_option_k):
+  // ph[k] sums the time of the segments ending at stamp k (1 plain walk, 2 window refill,
+  // 3 full tick); rounds counts stamp 0
+  unsigned long long ph[4] = {0, 0, 0, 0}, last = 0;
+  uint32_t rounds = 0;
+  __device__ __forceinline__ void phase(int k) {
+    const unsigned long long now = __builtin_amdgcn_s_memtime();
+    if (last) ph[k] += now - last;
+    last = now;
+    rounds += k == 0;
+  }
+#else
+  __device__ __forceinline__ void phase(int) {}
+#endif
+  // a draw was taken past the staged window (reserve's bound broken: flagged E_WINDOW)
+  __device__ __forceinline__ bool overrun() const { return left > (uint32_t)WIN_DRAWS; }
+  // one draw, consumed for its outcomes (draw_code); reserve() guarantees it is in the window
+  __device__ __forceinline__ uint32_t code() {
+    const uint32_t c = nxc;
+    ++n;
+    ++draws;
+    ++rd;
+    --left;
+    nxc = read();  // the next draw's code, one draw ahead (a byte of the window when left = 0)
+    return c;
+  }
+  // one draw as its double (rare): the code is consumed too, the value built from the words
+  // (an odd generation's twisted from the stored one before it, tg_core.h mt_pair)
+  __device__ __forceinline__ double random() {
+    uint32_t p = (pos >> 1) + n;
+    p = 2u * (p >= (uint32_t)MT_CODES ? p - (uint32_t)MT_CODES : p);
+    (void)code();
+    const WordPair w = FLOW ? mt_pair_ool_sc1(mt, p) : mt_pair_ool(mt, p);
+    return mt_double(w.w0, w.w1);
+  }
+  __device__ __forceinline__ double uniform(double a, double b) { return a + (b - a) * random(); }
+  // drain the DMAs (the window is reused as scratch); returns the state word to store: the
+  // entry's stale half, still stale, keeps its bits (listed or not); a half left in this launch
+  // is stale and not listed yet; none, if the lane regenerated the stale half itself
+  __device__ __forceinline__ uint32_t finish() {
+    if (primed) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    sync();
+    primed = loaded = false;
+    return pos | (stale == NONE ? 0u : entered ? MT_STALE : tag);
+  }
+};
+
+using RngCodes = RngCodesT<false>;
+
+__device__ __forceinline__ uint64_t readlane64(uint64_t v, int lane) {
+  const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)v, lane);
+  const uint32_t hi = __builtin_amdgcn_readlane((uint32_t)(v >> 32), lane);
+  return ((uint64_t)hi << 32) | lo;
+}
+// For every lane in `need`: regenerate the stale half of its env (the one not holding the
+// position in its state word), one env at a time, with the whole wave (wave_twist_gens: its
+// MT_HALF_GENS generations from the other half's last).  Must be reached by all 64 lanes.
+__device__ __forceinline__ void wave_refill(unsigned long long need, uint32_t* env_mt, uint8_t* env_mc,
+                                            uint32_t state, lds_u32* scratch) {
+  const uint32_t pos = state & MT_POS_MASK;
+  const uint32_t dst = (uint32_t)MT_HALF - mt_half(pos);
+  const uint64_t src_l = (uint64_t)(uintptr_t)(env_mt + regen_src_off(dst));
+  const uint64_t w_l = (uint64_t)(uintptr_t)env_mt;
+  const uint64_t c_l = (uint64_t)(uintptr_t)env_mc;
+  const int g0_l = (int)(dst / (uint32_t)MT_N);
+  while (need) {
+    const int L = __ffsll((long long)need) - 1;
+    need &= need - 1;
+    wave_twist_gens((const glb_u32*)(uintptr_t)readlane64(src_l, L),
+                    (glb_u32*)(uintptr_t)readlane64(w_l, L), (uint8_t*)(uintptr_t)readlane64(c_l, L),
+                    __builtin_amdgcn_readlane(g0_l, L), MT_HALF_GENS, true, scratch);
+  }
+}
+
+// 64-lane sum (wave64)
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+enum { ST_STEPS, ST_VALID, ST_TICKS, ST_DRAWS, ST_EPISODES, ST_EP_OVERFLOW, ST_REGENS, ST_WTICKS,
+       ST_COUNT };
+
+// 64-lane max (wave64)
+__device__ __forceinline__ int wave_max(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// In-kernel span stamps of the timed launches (tg_set_timing): each wave's lane 0 folds its
+// start and end (s_memrealtime: the 100 MHz constant clock) into one of KST_SLOTS
+// (min start, max end) pairs of the launch's record, with returnless atomics on 64 addresses;
+// flush_timing reduces them to the launch's span, first wave start to last wave end.  Null
+// record: not timed (a wave-uniform branch).
+constexpr int KST_SLOTS = 64;
+constexpr int KST_STRIDE = 16;  // u64 per slot: each slot's pair in a 128-B line of its own
+__device__ __forceinline__ unsigned long long kst_begin(const unsigned long long* ks) {
+  return ks ? __builtin_amdgcn_s_memrealtime() : 0ull;
+}
+__device__ __forceinline__ void kst_end(unsigned long long* ks, unsigned long long t0) {
+  if (ks && (threadIdx.x & 63) == 0) {
+    unsigned long long* const s = ks + KST_STRIDE * (blockIdx.x % KST_SLOTS);
+    atomicMin(s, t0);
+    atomicMax(s + 1, (unsigned long long)__builtin_amdgcn_s_memrealtime());
+  }
+}
+struct StepIO {
+  int32_t* __restrict__ actions;   // input; with policy >= 0 the step's actions are written here
+  double* __restrict__ obs;
+  int32_t* __restrict__ reward;
+  uint8_t* __restrict__ valid;
+  uint8_t* __restrict__ done;
+  double* __restrict__ final_obs;  // may be null
+  int policy;                      // -1: actions given; else TG_POLICY_* evaluated in the step
+                                   // (selects the kernels' POL instantiation)
+  uint64_t a0;                     // the policy's action seed and step index
+  int64_t t;
+  uint32_t tstep;                  // this step's index in the handle's step count (launch_step):
+                                   // an episode's length is tstep + 1 - its start step (S.ep.y)
+};
+
+__device__ __forceinline__ uint64_t sm64(uint64_t x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+// the synthetic policies (tg_policy_actions): a[t, g] = h(a0, g, t) % 9, or the k-th set bit
+// of available_mask with k = h % popcount (masked-uniform; h % 9 when nothing can run)
+__device__ __forceinline__ int policy_action(const Level& L, const Map& m, const Env& e,
+                                             int policy, uint64_t a0, int64_t g, int64_t t) {
+  const uint64_t h = sm64(sm64(a0 ^ sm64((uint64_t)g)) ^ (uint64_t)t);
+  int a = (int)(h % 9ull);
+  if (policy == TG_POLICY_MASKED) {
+    const uint32_t mk = available_mask(L, m, e);
+    const int c = __popc(mk);
+    if (c) {
+      uint32_t k = (uint32_t)(h % (uint64_t)c);
+      uint32_t mm = mk;
+      while (k--) mm &= mm - 1u;
+      a = __ffs(mm) - 1;
+    }
+  }
+  return a;
+}
+struct EpQueue {
+  tg_episode* __restrict__ eps;
+  int32_t* count;
+  int32_t cap;
+};
+
+// Completed episodes (auto-reset): wavefront ballot, popcount prefix, one atomic per wave.
+// The queue is drained by tg_episodes; if nobody drains it, the count must not run away (an
+// int32 that wraps would turn the bound check into an out-of-bounds store): a wave whose
+// records do not all fit clamps the count back to cap (atomicMin) after its add.  Between an
+// add and its clamp other waves can add, so the count stays below cap + the records of the
+// waves in flight (<= cap + n < 2^31 with cap <= 2^28 and n < 2^30); slots are compared
+// unsigned.  The records that do not fit are counted per wave in the wave's own block slot.
+// Must be reached by every lane of the wave.
+__device__ __forceinline__ void record_episodes(bool mine, int64_t g, int2& ep, uint32_t tstep,
+                                                const EpQueue& q, unsigned long long* stats,
+                                                int64_t sl) {  // sl: the wave's stats slot
+  const unsigned long long b = __ballot(mine);
+  if (!b) return;
+  const int lane = threadIdx.x & 63;
+  const int first = __ffsll((long long)b) - 1;
+  const int cnt = __popcll(b);
+  int base = 0;
+  if (lane == first) {
+    base = atomicAdd(q.count, cnt);
+    if ((uint32_t)base + (uint32_t)cnt > (uint32_t)q.cap) {
+      atomicMin(q.count, q.cap);
+      const uint32_t lost = (uint32_t)base >= (uint32_t)q.cap
+                                ? (uint32_t)cnt : (uint32_t)base + (uint32_t)cnt - (uint32_t)q.cap;
+      atomicAdd(&stats[(size_t)sl * ST_COUNT + ST_EP_OVERFLOW], (unsigned long long)lost);
+    }
+  }
+  base = __shfl(base, first, 64);
+  if (mine) {
+    const uint32_t slot = (uint32_t)base + (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
+    if (slot < (uint32_t)q.cap) {
+      tg_episode r;
+      r.env = g;
+      r.ret = ep.x;
+      r.len = (int32_t)(tstep + 1u - (uint32_t)ep.y);
+      q.eps[slot] = r;
+    }
+    ep = make_int2(0, (int32_t)(tstep + 1u));  // the next episode starts with the next step
+  }
+}
+
+// Launch counters: every step kernel has a per-block slot of `part` ([grid][ST_COUNT]) and the
+// host sums the slots on demand (one counter word per launch took ~32k same-line atomics:
+// ~370 us at ~88 atomics/us).  Each wave's lane 0 adds its sums into its block's slot with
+// returnless atomics (no contention across blocks; no barrier, so every wave exits as soon as
+// it is done).  Must be reached by every lane of the wave.
+// wave_ticks: the wave's longest lane's ticks (the tick loop's trip count, lane efficiency).
+__device__ __forceinline__ void wave_stats(unsigned long long* __restrict__ part, int steps,
+                                           int valid, int ticks, int draws, int episodes,
+                                           int regens = 0, bool wave_ticks = false,
+                                           int64_t sl = -1) {  // slot: blockIdx.x by default
+  // a counter that is 0 on every lane (k_run's steps / valid, most waves' episodes) skips its
+  // six cross-lane steps: the reductions sit in the option waves' epilogue, on the tail
+  auto sum = [](int x) { return __ballot(x != 0) ? wave_sum(x) : 0; };
+  const int v[5] = {sum(steps), sum(valid), sum(ticks), sum(draws), sum(episodes)};
+  const int wt = wave_ticks ? wave_max(ticks) : 0;
+  if ((threadIdx.x & 63) == 0) {
+    unsigned long long* const slot = part + (size_t)(sl < 0 ? (int64_t)blockIdx.x : sl) * ST_COUNT;
+#pragma unroll
+    for (int c = 0; c < 5; ++c)
+      if (v[c]) atomicAdd(&slot[c], (unsigned long long)v[c]);
+    if (regens) atomicAdd(&slot[ST_REGENS], (unsigned long long)regens);
+    if (wt) atomicAdd(&slot[ST_WTICKS], (unsigned long long)wt);
+  }
+}
+
+// wave_stats for a wave whose only live lane is lane 0 (k_py1, k_serve1): lane 0's own values,
+// no cross-lane reductions (~0.5 us of a one-env call)
+__device__ __forceinline__ void lane0_stats(unsigned long long* __restrict__ part, int steps,
+                                            int valid, int ticks, int draws, int episodes,
+                                            int regens = 0, bool wave_ticks = false) {
+  if ((threadIdx.x & 63) != 0) return;
+  unsigned long long* const slot = part + (size_t)blockIdx.x * ST_COUNT;
+  const int v[5] = {steps, valid, ticks, draws, episodes};
+#pragma unroll
+  for (int c = 0; c < 5; ++c)
+    if (v[c]) atomicAdd(&slot[c], (unsigned long long)v[c]);
+  if (regens) atomicAdd(&slot[ST_REGENS], (unsigned long long)regens);
+  if (wave_ticks && ticks) atomicAdd(&slot[ST_WTICKS], (unsigned long long)ticks);
+}
+
+// finish one env-step: obs/reward/valid/done rows, episode counters, optional auto-reset.
+// keep != nullptr: the obs row is returned there instead of stored (the caller stores it).
+// The option waves' epilogue computes its obs rows by f64 division: the quotient table
+// (tg_core.h obs_div) is a global load on their tail, and by stamps the epilogue was ~4,000
+// cycles shorter without it (profiles/r04/stamps_divq_uniform_r04k.log); k_classify, whose
+// waves are not a tail, keeps the table
+__device__ __forceinline__ Level level_div(const Level& L) {
+  Level d = L;
+  d.obs_q = nullptr;
+  return d;
+}
+// VALID: the valid row is this call's (k_classify writes every env's valid row itself, coalesced:
+// k_run's scattered byte store cost a 32-B write granule per listed env)
+template <bool AUTORESET, bool FINAL, bool VALID = true, class R>
+__device__ __forceinline__ void finish_step(const Level& L, Env& e, R& rng, int64_t i,
+                                            const StepResult& r, int2& ep, const StepIO& io,
+                                            double* keep = nullptr) {
+  if (rng.overrun()) e.f |= E_WINDOW;
+  double o[9];
+  observe(L, e, o);  // get_state (TG/:94)
+  io.reward[i] = r.reward;
+  if (VALID) io.valid[i] = (uint8_t)r.ran;
+  io.done[i] = (uint8_t)r.done;
+  ep.x += r.reward;  // (ep.y, the episode's start step, stays: no store for a reward-None step)
+  if (FINAL) store_obs(io.final_obs, i, o);
+  if (AUTORESET && r.done) {
+    reset_env(L, e, rng);
+    observe(L, e, o);
+  }
+  if (keep) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) keep[k] = o[k];
+  } else {
+    store_obs(io.obs, i, o);
+  }
+}
+
+// The obs rows of a wave's 64 consecutive envs (4,608 B) through LDS: lane l stores the
+// 8-B words l, l+64, ... of the span, so each store instruction writes 512 contiguous bytes
+// (a lane storing its own 72-B row touches ~36 cache lines per instruction).  Rows of envs
+// not in `mask` are left alone.  Every lane of the wave must reach it.
+__device__ __forceinline__ void store_obs_wave(double* __restrict__ out, int64_t wave_first,
+                                               unsigned long long mask, const double o[9],
+                                               double* __restrict__ stage) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) stage[lane * 9 + k] = o[k];
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  double* const dst = out + wave_first * 9;
+#pragma unroll
+  for (int j = 0; j < 9; ++j) {
+    const int w = j * 64 + lane;
+    if ((mask >> (w / 9)) & 1ull) __builtin_nontemporal_store(stage[w], dst + w);
+  }
+}
+
+// ---- one-pass step: one lane per env, the option runs in place (TG_MODE_DIRECT) ----------
+constexpr int POL_IMMEDIATE = -2;  // k_step's action is io.a0 (tg_step1), not an array entry
+// POL: -1 actions given; POL_IMMEDIATE one action for all (tg_step1); else the TG_POLICY_*
+// evaluated here (tg_rollout).  A template
+// parameter, so the per-step kernels carry none of the policy's code or registers.
+// One step of env i (lane i's; live iff i < n) with the level in LDS (trig, m) and the wave's
+// code window wscr: k_step's body, also k_serve1's private-stream step.  Every lane of the wave
+// must reach it.
+template <bool AUTORESET, bool FINAL, int POL, bool ONE = false>  // ONE: only lane 0 live (k_serve1)
+__device__ __forceinline__ StepResult step_env(const Soa& S, int64_t n, const Level& L,
+                                         const uint32_t* trig, const Map& m, lds_u8* wscr,
+                                         int64_t i, const StepIO& io, const EpQueue& q,
+                                         int64_t g0, unsigned long long* __restrict__ stats,
+                                         uint32_t* __restrict__ err_or) {
+  const bool live = i < n;
+  StepResult r{0, 0, 0, 0};
+  uint32_t draws = 0;
+  int lregen = 0;  // halves this lane regenerated in its option loop
+  Env e;
+  e.mti = 0u;
+  int2 ep = make_int2(0, 0), ep_in = ep;
+  if (live) {
+    unpack(S.st4[i], S.ang[i], e);
+    ep = S.ep[i];
+    ep_in = ep;
+    RngCodes rng(S.mt + i * MT_STORE, S.mc + i * MT_CODES, e.mti, wscr);
+    int act;
+    if constexpr (POL >= 0) {
+      act = policy_action(L, m, e, POL, io.a0, g0 + i, io.t);
+      if (io.actions) io.actions[i] = act;
+    } else if constexpr (POL == POL_IMMEDIATE) {
+      act = (int)(int64_t)io.a0;  // tg_step1: the action is a kernel argument
+    } else {
+      act = io.actions[i];
+    }
+    r = env_step(L, trig, m, e, act, rng);
+    finish_step<AUTORESET, FINAL>(level_div(L), e, rng, i, r, ep, io);
+    e.mti = rng.finish();
+    draws = rng.draws;
+    lregen = (int)rng.regens;
+    if (e.f & E_MASK) atomicOr(err_or, e.f & E_MASK);
+  }
+  // one pass, no classify pass after it: regenerate the halves left in this launch now
+  const unsigned long long need = __ballot(live && (e.mti & MT_STALE));
+  wave_refill(need, S.mt + (live ? i : 0) * MT_STORE,
+              S.mc + (live ? i : 0) * MT_CODES, e.mti,
+              (lds_u32*)wscr);
+  e.mti &= ~(MT_STALE | MT_LISTED);
+  if (AUTORESET) record_episodes(live && r.done, g0 + i, ep, io.tstep, q, stats, blockIdx.x);
+  if (live) {
+    S.st4[i] = pack(e);
+    S.ang[i] = make_double2(e.ang0, e.ang1);
+    if (ep.x != ep_in.x || ep.y != ep_in.y) S.ep[i] = ep;  // a reward-None step changes nothing
+  }
+  if constexpr (ONE)
+    lane0_stats(stats, live ? 1 : 0, r.ran, r.ticks, (int)draws, AUTORESET ? (live && r.done) : 0,
+                __popcll(need) + lregen, true);
+  else
+    wave_stats(stats, live ? 1 : 0, r.ran, r.ticks, (int)draws, AUTORESET ? (live && r.done) : 0,
+               __popcll(need) + wave_sum(lregen), true);
+  return r;
+}
+
+// ---- the compacted step's lists (k_classify / k_run, tg_kernels.h; k_flow's chunks, tg_flow.h) --
+constexpr int SHARDS = 8;  // the stale-MT-half refill lists: one per XCD (k_regen's waves of XCD x drain list x)
+// the worklists' shards (k_classify's workgroup b appends to shard b % WSHARDS): each
+// (option, shard) counter takes one returning atomic per workgroup that lists an env of that
+// option, so more shards spread a launch's ~4k x 10 atomics over more words
+#ifndef TG_WSHARDS
+#define TG_WSHARDS 8
+#endif
+constexpr int WSHARDS = TG_WSHARDS;
+// Worklists: one per option, and one (L_RESET) of the envs whose option cannot run but which
+// enter the step done with auto-reset on (stepped with auto-reset off until done, then on):
+// k_run resets them (reward None, no option), so k_classify carries no reset path (the gauss
+// pair's f64 library code held it at 79 VGPRs, 6 waves per SIMD; without it 58, 8 waves)
+constexpr int L_RESET = O_COUNT;
+constexpr int NLIST = O_COUNT + 1;
+constexpr int kOrderH[NLIST] = {O_JUMP_LEFT, O_JUMP_RIGHT, O_GO_LEFT,     O_GO_RIGHT,
+                                O_DOWN_LEFT, O_DOWN_RIGHT, O_UP_LADDER,   O_DOWN_LADDER,
+                                O_INTERACT,  L_RESET};
+struct RunPos {
+  int of[NLIST];  // run position of list k (kOrder's inverse)
+};
+constexpr RunPos make_runpos() {
+  RunPos r{};
+  for (int j = 0; j < NLIST; ++j) r.of[kOrderH[j]] = j;
+  return r;
+}
+constexpr RunPos kRunPos = make_runpos();
+constexpr int NSEG = NLIST * WSHARDS;  // segment = run position * WSHARDS + shard
+static_assert(NSEG <= 2 * RUN_BLOCK, "k_run's prefix: two segments per thread");
+constexpr int NCTR = NSEG;      // the worklist counters
+constexpr int CTR_STRIDE = 32;  // counters 128 B apart
+struct Work {
+  int32_t* __restrict__ lists;   // [NSEG][shard_cap], segment = run position * WSHARDS + shard
+  // the listed envs' state, in worklist order (written by k_classify, which has loaded it
+  // anyway): k_run reads its chunk's 64 records coalesced, in one round trip with the list
+  // entries, instead of a dependent gather of 16 + 16 + 8 scattered bytes per lane
+  uint4* __restrict__ wst4;      // [NSEG][shard_cap]
+  double2* __restrict__ wang;
+  int2* __restrict__ wep;
+  int32_t* __restrict__ ctr;     // [NCTR * CTR_STRIDE], this step's counters
+  int32_t* __restrict__ ctr_next;  // the other parity's, zeroed here for the next step
+  // stale MT halves, one list per shard (= blockIdx.x % SHARDS, the XCD), appended across the
+  // pending steps: list x at refill[x * rcap ..], its length at rcnt[x * CTR_STRIDE]
+  uint32_t* __restrict__ refill;  // env | source half
+  int32_t* __restrict__ rcnt;
+  int64_t rcap;
+  int64_t shard_cap;
+};
+// k_regen (tg_kernels.h) drains the stale-MT-half refill lists every REGEN_STEPS compact steps
+constexpr int REGEN_STEPS = 16;
+// regen_ctr, per set: the 8 grab counters, then the 8 list lengths (k_classify's rcnt)
+constexpr int RCTR_LIST = 8;
+constexpr int RCTR_N = 16;
+}  // namespace
+
+// k_flow<AR, POL> is instantiated in its own translation unit, tg_flow.hip, which is built
+// without MachineLICM (the pass hoisted values out of the flow's work loop and
+// held them live across it, 123-182 VGPRs; without it 121-129, 4 waves per SIMD)
+namespace tg {
+const void* flow_kernel(bool ar, int pol);
+}

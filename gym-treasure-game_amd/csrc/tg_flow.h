@@ -1,7 +1,8 @@
 // tg_flow.h — k_flow: tg_rollout's K steps in ONE launch, each 64-env chunk advancing to its
 // next step as soon as its own envs have finished the current one (TG_MODE_FLOW, §8f row 3).
-// Included by tg_amd.hip inside its anonymous namespace, after the per-step kernels whose
-// pieces it reuses (RngCodesT, finish_step, store_obs_wave, record_episodes, wave_stats).
+// Built on tg_dev.h's pieces of the per-step kernels (RngCodesT, finish_step, store_obs_wave,
+// record_episodes, wave_stats).  tg_flow.hip instantiates k_flow; tg_amd.hip includes this header
+// for the Flow / FlowIO types and constants its host code fills in (launch_flow).
 //
 // Why: the reference's step is per env (TG/:91-96 -> OP/:20-36): env i's step
 // t + 1 depends on env i's step t only.  The per-step kernels put a batch-wide barrier after
@@ -44,6 +45,9 @@
 // Every spin is bounded (FLOW_DEADLINE of the 100 MHz clock): a wave that waits longer sets
 // TG_ERR_FLOW and its sub-problem's done word, so a bug ends the launch instead of hanging it.
 #pragma once
+#include "tg_dev.h"
+
+namespace {
 
 constexpr int FLOW_MAX_K = REGEN_STEPS;  // steps per launch (the MT slack: k_regen every 16)
 constexpr int FLOW_MAX_PARTS = 8;        // sub-problems: one per XCD
@@ -164,6 +168,8 @@ __device__ __forceinline__ uint32_t xcc_id() {
   return x;
 }
 
+}  // namespace
+
 #ifdef TG_FLOW_DBG
 #include "tg_flow_diag.h"  // (diagnostic builds only: the bring-up instrumentation)
 #else
@@ -180,22 +186,7 @@ __device__ __forceinline__ uint32_t xcc_id() {
 #define FLOW_DIAG_CLASSIFY(c, t) (void)0
 #endif
 
-#ifndef TG_FLOW_TU  // (launched by tg_amd.hip's host code: the main unit only)
-// the XCC ids the device's workgroups run on (one bit each): the flow's sub-problems
-__global__ void k_census(uint32_t* mask) {
-  if (threadIdx.x == 0) atomicOr(mask, 1u << (xcc_id() & 31u));
-}
-// after every k_flow launch, on its stream (one wave): a sub-problem whose chunks did not all
-// finish step K - 1 sets TG_ERR_FLOW (no wave ran on its XCD; see "Coherence" above)
-__global__ void k_flow_check(const int32_t* __restrict__ ctl, int P, int32_t C,
-                             uint32_t* __restrict__ err_or) {
-  const int x = (int)threadIdx.x;
-  if (x < P) {
-    const int Cx = (C - x + P - 1) / P;
-    if (Cx > 0 && ctl[(int64_t)x * CTL_WORDS + FC_FIN * FC_STRIDE] != Cx) atomicOr(err_or, E_FLOW);
-  }
-}
-#endif
+namespace {
 
 // 4 waves per SIMD (<= 128 VGPRs; built without MachineLICM, tg_flow.hip: 123-131 VGPRs
 // unconstrained) — r05j A/B: uniform 0.1111 vs 0.1163 ms per step at 3 waves, masked 0.3309 vs
@@ -548,3 +539,5 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4))) void
   if (lane == 0) FLOW_EV(9, x, 0, 0, 0);
   kst_end(ks, kt0);
 }
+
+}  // namespace

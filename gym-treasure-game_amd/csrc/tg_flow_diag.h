@@ -10,8 +10,14 @@
 // Host side: flow_diag_setup() before a launch (buffers, the Flow's diagnostic pointers) and
 // flow_diag_after() after it (watches the progress words for up to 8 s, writes the event log).
 #pragma once
+#include <unistd.h>
 
-#define FLOW_DBG(code, a, b, c)                                                                  \
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#define FLOW_DBG(code, a, b, c)                                                                 \
   do {                                                                                           \
     const int64_t gw_ = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) >> 6;                        \
     if (f.dbg && lane == 0 && gw_ < 4096) {                                                      \
@@ -136,8 +142,7 @@ constexpr uint32_t FLOW_EVW = 1024;
     }                                                                                            \
   } while (0)
 
-#ifndef TG_FLOW_TU
-// ---- host side (tg_amd.hip launch_flow) ---------------------------------------------------------
+// ---- host side (tg_amd.hip's launch_flow calls it; tg_flow.hip compiles it unused) ---------------
 // the diagnostic buffers behind the Flow's dbg / dbgc / dbgl pointers
 static uint32_t* g_flow_dbg_host = nullptr;  // the progress words (host-mapped)
 inline int flow_diag_setup(tg_batch* h, Flow& f) {
@@ -224,4 +229,3 @@ inline int flow_diag_after(tg_batch* h, const Flow& f, int k, int bpc, hipStream
   }
   return TG_OK;
 }
-#endif  // TG_FLOW_TU

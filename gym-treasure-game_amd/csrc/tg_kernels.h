@@ -1,0 +1,725 @@
+// tg_kernels.h — the batch kernels: creation and reset, the one-pass and the two-pass step,
+// k_regen, the flow mode's census and check, and the small per-env queries.  Compiled by
+// tg_amd.hip only, whose host code launches them; the device helpers they share with k_flow are
+// tg_dev.h's.
+#pragma once
+#include "tg_dev.h"
+#include "tg_flow.h"
+#include "tg_policy_mlp.h"
+
+namespace {
+
+// every in-kernel span record to (no start, no end) (kst_begin / kst_end, tg_dev.h)
+__global__ void k_kst_init(unsigned long long* ks, int64_t slots) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < slots) {
+    ks[KST_STRIDE * i] = ~0ull;
+    ks[KST_STRIDE * i + 1] = 0ull;
+  }
+}
+
+// ---- creation and reset ---------------------------------------------------------------------
+// random.seed(seed0 + i): init_by_array into half 0's last stored slot (tg_core.h init_mt);
+// k_gen_twist then makes the ring's 2 x MT_HALF_GENS generations from it, and k_reset (mask NULL)
+// performs the constructor's game build (_TreasureGameImpl.__init__, IM/:31-53: 4 draws) —
+// tg_create.
+__global__ __launch_bounds__(BLOCK) void k_create(Soa S, int64_t n, uint64_t seed0,
+                                                   const uint32_t* __restrict__ genrand) {
+  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= n) return;
+  seed_mt(S.mt + i * MT_STORE + MT_SEED_OFF, genrand, seed0 + (uint64_t)i);
+  Env e{};
+  e.mti = 0u;
+  S.st4[i] = pack(e);
+  S.ang[i] = make_double2(0.0, 0.0);
+  S.ep[i] = make_int2(0, 0);
+}
+// `gens` generations for every env, in sequence after the stored words at offset src: ring
+// generations g0, g0 + 1, ... (codes; words of the even ones; tg_create, tg_write_state)
+__global__ __launch_bounds__(BLOCK) void k_gen_twist(Soa S, int64_t n, uint32_t src, int g0,
+                                                     int gens) {
+  __shared__ __attribute__((aligned(16))) uint32_t scratch[BLOCK / 64][MT_N];
+  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  unsigned long long need = __ballot(i < n);
+  const int64_t i0 = i - (threadIdx.x & 63);
+  while (need) {
+    const int L = __ffsll((long long)need) - 1;
+    need &= need - 1;
+    const int64_t e = i0 + L;
+    wave_twist_gens((const glb_u32*)(S.mt + e * MT_STORE + src), (glb_u32*)(S.mt + e * MT_STORE),
+                    S.mc + e * MT_CODES, g0, gens, false, (lds_u32*)scratch[threadIdx.x >> 6]);
+  }
+}
+
+// the draw codes of the ring's first generation (stored words [0, 624)) of every env (tg_write_state)
+__global__ __launch_bounds__(BLOCK) void k_gen_codes(Soa S, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i < n) gen_codes(S.mt + i * MT_STORE, S.mc + i * MT_CODES);
+}
+
+__global__ __launch_bounds__(BLOCK) void k_reset(Soa S, int64_t n, Level L,
+                                                  const uint8_t* __restrict__ mask,
+                                                  double* __restrict__ obs, uint32_t tstep) {
+  __shared__ __attribute__((aligned(16))) uint32_t scratch[BLOCK / 64][MT_N];
+  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  const bool live = i < n;
+  const bool reset = live && (!mask || mask[i]);
+  Env e;
+  e.mti = 0u;
+  if (live) {
+    unpack(S.st4[i], S.ang[i], e);
+    if (reset) {
+      Rng rng(S.mt + i * MT_STORE, e.mti, S.mc + i * MT_CODES);
+      reset_env(L, e, rng);
+      e.mti = rng.finish();
+    }
+    if (obs) {
+      double o[9];
+      observe(L, e, o);
+      store_obs(obs, i, o);
+    }
+  }
+  const bool stale = reset && (e.mti & MT_STALE);
+  wave_refill(__ballot(stale), S.mt + (live ? i : 0) * MT_STORE, S.mc + (live ? i : 0) * MT_CODES, e.mti,
+              (lds_u32*)scratch[threadIdx.x >> 6]);
+  if (reset) {
+    e.mti &= ~(MT_STALE | MT_LISTED);
+    S.st4[i] = pack(e);
+    S.ang[i] = make_double2(e.ang0, e.ang1);
+    S.ep[i] = make_int2(0, (int32_t)tstep);  // the episode starts with the next step
+  }
+}
+
+// ---- one-pass step (TG_MODE_DIRECT): step_env (tg_dev.h) per lane -------------------------
+template <bool AUTORESET, bool FINAL, int POL = -1>
+__global__ __launch_bounds__(BLOCK) void k_step(Soa S, int64_t n, Level L,
+                                                 const uint32_t* __restrict__ grid, StepIO io,
+                                                 EpQueue q, int64_t g0,
+                                                 unsigned long long* __restrict__ stats,
+                                                 uint32_t* __restrict__ err_or,
+                                                 unsigned long long* __restrict__ ks) {
+  const unsigned long long kt0 = kst_begin(ks);
+  __shared__ __attribute__((aligned(16))) uint8_t win[(BLOCK / 64) * WIN_WAVE_BYTES];
+  LEVEL_IN_LDS();
+  lds_u8* const wscr = (lds_u8*)win + (threadIdx.x >> 6) * WIN_WAVE_BYTES;
+  step_env<AUTORESET, FINAL, POL>(S, n, L, trig, m, wscr, (int64_t)blockIdx.x * BLOCK + threadIdx.x,
+                                  io, q, g0, stats, err_or);
+  kst_end(ks, kt0);
+}
+
+// ---- two-pass compacted step (TG_MODE_COMPACT) -------------------------------------------
+// Pass 1, k_classify: one lane per env (coalesced).  Evaluates option_list[a].can_run();
+// envs whose option cannot run finish here (reward None, obs/done rows written, state
+// unchanged); the rest are appended to per-option worklists.  Appends are aggregated per
+// workgroup in LDS and the counters are sharded 8 ways (blockIdx % 8) across cache lines (one
+// word alone saturates at ~88 atomics/us, MI355X_MICROARCH.md "dequeue").
+// Pass 2, k_run: wave w runs chunk w (64 envs) of the worklists concatenated in run order
+// (options in kOrder, each option's 8 shards).  Only the options are padded to whole chunks
+// (round 2 padded every shard), so every wave holds ONE option: a wave-uniform k selects a loop
+// specialised to that option's primitive actions.  (Round 3 also tried worklists per (option,
+// predicted length class), which raised lane efficiency from 0.53 to 0.84 but ran 2-5 % slower:
+// DESIGN.md §3.1.)
+// worklist order = the order the chunks' loads reach HBM at the kernel's start (all option
+// waves are resident at once and issue their loads together): the jump waves first, whose
+// ticks are the slowest in wall time (~2,100 cycles each) and which end the kernel, then the
+// long go walks (mean 56 ticks), drops, ladders, interact.  A/B against go
+// first: 0.1366 vs 0.1400 ms.
+__constant__ int kOrder[NLIST] = {O_JUMP_LEFT, O_JUMP_RIGHT, O_GO_LEFT,     O_GO_RIGHT,
+                                  O_DOWN_LEFT, O_DOWN_RIGHT, O_UP_LADDER,   O_DOWN_LADDER,
+                                  O_INTERACT,  L_RESET};
+__constant__ int kSegBase[NLIST] = {kRunPos.of[0] * WSHARDS, kRunPos.of[1] * WSHARDS,
+                                      kRunPos.of[2] * WSHARDS, kRunPos.of[3] * WSHARDS,
+                                      kRunPos.of[4] * WSHARDS, kRunPos.of[5] * WSHARDS,
+                                      kRunPos.of[6] * WSHARDS, kRunPos.of[7] * WSHARDS,
+                                      kRunPos.of[8] * WSHARDS, kRunPos.of[9] * WSHARDS};
+
+// 8 waves per SIMD: its 98-106 SGPRs (the level, the step's pointers) held it to 7; forced, 32-55
+// of them spill to VGPR lanes (no VGPR spills, 60 VGPRs).  A/B r04r: uniform 0.1246 vs 0.1258 ms
+// per step in each of 4 rounds; masked within its spread
+template <bool AUTORESET, bool FINAL, int POL = -1>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_classify(
+    Soa S, int64_t n, Level L, const uint32_t* __restrict__ grid, StepIO io, EpQueue q, Work w,
+    int64_t g0, unsigned long long* __restrict__ stats, uint32_t* __restrict__ err_or,
+    unsigned long long* __restrict__ ks) {
+  const unsigned long long kt0 = kst_begin(ks);
+  __shared__ int bcnt[NLIST], bbase[NLIST];
+  __shared__ int rwc[BLOCK / 64], rbase;  // stale halves per wave; the workgroup's list range
+  // the obs staging reuses the level's LDS: nothing reads the grid after the second barrier
+  // below (finish_step / reset_env use only L), so 18.4 KB instead of 20.8 KB per workgroup
+  __shared__ union {
+    LdsLevel lv;
+    double ostage[BLOCK * 9];
+  } lds;
+  LdsLevel& lv = lds.lv;
+  double* const ostage = lds.ostage;
+  double orow[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  const bool live = i < n;
+  const int lane = threadIdx.x & 63;
+  // every load this lane may need, issued before the level staging and the barriers so their
+  // latencies overlap (the angles / episode words only matter if the option cannot run)
+  uint4 s4 = make_uint4(0, 0, 0, 0);
+  int32_t act = 0;
+  double2 a2 = make_double2(0.0, 0.0);
+  int2 ep = make_int2(0, 0);
+  if (live) {
+    s4 = S.st4[i];
+    if constexpr (POL < 0) act = io.actions[i];
+    a2 = S.ang[i];
+    ep = S.ep[i];
+  }
+  if (threadIdx.x < NLIST) bcnt[threadIdx.x] = 0;
+  if (blockIdx.x == 0)
+    for (int c = threadIdx.x; c < NCTR; c += BLOCK) w.ctr_next[c * CTR_STRIDE] = 0;
+  stage_level(lv, grid, L);  // includes the barrier
+  const Map m{reinterpret_cast<const uint8_t*>(lv.grid), L.W, L.H};
+  int k = -1;
+  bool runs = false;
+  Env e;
+  e.mti = 0u;
+  if (live) {
+    unpack_st4(s4, e);
+    if constexpr (POL >= 0) {  // the rollout's on-device policy (tg_rollout)
+      act = policy_action(L, m, e, POL, io.a0, g0 + i, io.t);
+      if (io.actions) io.actions[i] = act;
+    }
+    k = option_index(act);
+    runs = k >= 0 && can_run(L, m, e, k);
+    if (k < 0) e.f |= E_ACTION;
+  }
+  // every env's valid row, coalesced (reward None unless its option runs; k_run writes the
+  // listed envs' other rows)
+  if (live) io.valid[i] = (uint8_t)runs;
+  // entering done with auto-reset on and no option to run: reset in k_run (L_RESET)
+  const bool rst = AUTORESET && live && !runs && is_done(e);
+  const int bk = runs ? k : rst ? L_RESET : -1;  // the env's worklist
+  // halves left stale and not listed yet go on this step's refill list (MT_LISTED); k_regen
+  // regenerates the lists of several steps at once (a lane that needs a half first does it
+  // itself: the ring leaves >= ~2,400 draws of slack, launch_step)
+  // (dense lists: a drain of a few steps' lists spreads one half per wave, where the per-wave
+  // regions of round 4 left a wave with the few regions holding 3-4 halves for ~0.1 ms; one
+  // atomic per workgroup, beside the worklists' below: per wave, ~2,000 returning atomics per
+  // counter and step at the masked policy's rate serialised k_classify, 30.8 -> 39.2 us)
+  const bool stale = live && (e.mti & (MT_STALE | MT_LISTED)) == MT_STALE;
+  int srank = 0;
+  {
+    const unsigned long long b = __ballot(stale);
+    srank = __popcll(b & ((1ull << lane) - 1ull));
+    if (lane == 0) rwc[threadIdx.x >> 6] = __popcll(b);
+    if (stale) e.mti |= MT_LISTED;
+  }
+  // workgroup-local slots: one LDS atomic per wave and option present in the wave (the
+  // wave's lanes are matched option by option)
+  int slot = 0;
+  {
+    unsigned long long pend = __ballot(bk >= 0);
+    while (pend) {
+      const int first = __ffsll((long long)pend) - 1;
+      const int b0 = __builtin_amdgcn_readlane(bk, first);
+      const unsigned long long b = __ballot(bk == b0);
+      int base = 0;
+      if (lane == first) base = atomicAdd(&bcnt[b0], __popcll(b));
+      base = __shfl(base, first, 64);
+      if (bk == b0) slot = base + __popcll(b & ((1ull << lane) - 1ull));
+      pend &= ~b;
+    }
+  }
+  __syncthreads();
+  // the workgroup's worklist ranges: issue the global atomics now, use them after the
+  // reward-None envs are finished (their latency overlaps that work)
+  const int shard = blockIdx.x % SHARDS, wshard = blockIdx.x % WSHARDS;
+  int my_base = 0;
+  if (threadIdx.x < NLIST) {
+    const int c = bcnt[threadIdx.x];
+    my_base = c ? atomicAdd(&w.ctr[(kSegBase[threadIdx.x] + wshard) * CTR_STRIDE], c) : 0;
+  } else if (threadIdx.x == 64) {  // (another wave than the worklists' atomics)
+    int c = 0;
+#pragma unroll
+    for (int v = 0; v < BLOCK / 64; ++v) c += rwc[v];
+    my_base = c ? atomicAdd(&w.rcnt[shard * CTR_STRIDE], c) : 0;
+  }
+  const uint4 s4w = pack(e);  // the state the worklist copy carries (listed half, E_ACTION)
+
+  // envs whose option cannot run: reward None, state unchanged (TG/:91-96, OP/:22-23); not
+  // done, or auto-reset off (the others are k_run's, L_RESET)
+  const bool fin = live && !runs && !rst;
+  if (fin) {
+    e.ang0 = a2.x;
+    e.ang1 = a2.y;
+    Rng rng(S.mt + i * MT_STORE, e.mti, S.mc + i * MT_CODES);  // no draws without a reset
+    StepResult r{0, 0, (int)is_done(e), 0};
+    finish_step<false, FINAL, false>(L, e, rng, i, r, ep, io, orow);
+    if (e.f & E_MASK) atomicOr(err_or, e.f & E_MASK);
+  }
+  const int2 ep_in = ep;
+  store_obs_wave(io.obs, i - lane, __ballot(fin), orow, ostage + (threadIdx.x & ~63) * 9);
+  if (fin) {
+    const uint4 s4n = pack(e);
+    if (s4n.x != s4.x || s4n.y != s4.y || s4n.z != s4.z || s4n.w != s4.w) {  // reset / flag
+      S.st4[i] = s4n;
+      S.ang[i] = make_double2(e.ang0, e.ang1);
+    }
+    // reward None: the return and the episode's start step are unchanged unless it ended
+    if (ep.x != ep_in.x || ep.y != ep_in.y) S.ep[i] = ep;
+  }
+  if (threadIdx.x < NLIST) bbase[threadIdx.x] = my_base;
+  if (threadIdx.x == 64) rbase = my_base;
+  __syncthreads();
+  if (stale) {
+    int at = rbase + srank;
+    for (int v = 0; v < (int)(threadIdx.x >> 6); ++v) at += rwc[v];
+    w.refill[shard * w.rcap + at] = (uint32_t)i | (mt_half(e.mti & MT_POS_MASK) ? 0x80000000u : 0u);
+  }
+  if (bk >= 0) {
+    const int64_t at = (int64_t)(kSegBase[bk] + wshard) * w.shard_cap + bbase[bk] + slot;
+    w.lists[at] = (int32_t)i;
+    w.wst4[at] = s4w;
+    w.wang[at] = a2;
+    w.wep[at] = ep;
+  }
+  wave_stats(stats, live ? 1 : 0, runs ? 1 : 0, 0, 0, 0);
+  kst_end(ks, kt0);
+}
+
+#ifdef TG_DIAG_STAMPS
+// DIAGNOSTIC BUILD ONLY (scripts/diag_stamps.py): per-wave s_memtime stamps of k_run
+constexpr int NSTAMP = 11;
+// per wave: 4 durations/counts, 100 MHz start and end, the option loop's phases (walk, refill,
+// full tick: lane 0's sums) and rounds
+constexpr int NSTAMP_WAVES = 1 << 17;
+__device__ unsigned long long g_stamps[NSTAMP_WAVES * NSTAMP];
+#define TG_STAMP(v) v = __builtin_amdgcn_s_memtime()
+#else
+#define TG_STAMP(v) (void)0
+#endif
+
+template <bool AUTORESET, bool FINAL>
+__global__ __launch_bounds__(RUN_BLOCK) void k_run(Soa S, int64_t n, Level L,
+                                                const uint32_t* __restrict__ grid, StepIO io,
+                                                EpQueue q, Work w, int64_t g0,
+                                                unsigned long long* __restrict__ stats,
+                                                uint32_t* __restrict__ err_or,
+                                                unsigned long long* __restrict__ ks) {
+  const unsigned long long kt0 = kst_begin(ks);
+  // the worklists in run order: pre[s] = envs listed before segment s (exclusive prefix of the
+  // counters, two segments per thread), then per option (run order j) its first segment's
+  // prefix and its start in the chunk space, where each option is padded to whole chunks
+  __shared__ int pre[NSEG + 1];
+  __shared__ int wtot[RUN_BLOCK / 64];
+  __shared__ int ostart[NLIST + 1], oraw[NLIST + 1];
+  {
+    const int s0 = 2 * (int)threadIdx.x, ln = threadIdx.x & 63;
+    const int c0 = s0 < NSEG ? w.ctr[s0 * CTR_STRIDE] : 0;
+    const int c1 = s0 + 1 < NSEG ? w.ctr[(s0 + 1) * CTR_STRIDE] : 0;
+    int v = c0 + c1;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int y = __shfl_up(v, o, 64);
+      if (ln >= o) v += y;
+    }
+    if (ln == 63) wtot[threadIdx.x >> 6] = v;
+    __syncthreads();
+    for (int wv = 0; wv < (int)(threadIdx.x >> 6); ++wv) v += wtot[wv];
+    const int excl = v - c0 - c1;
+    if (s0 < NSEG) pre[s0] = excl;
+    if (s0 + 1 < NSEG) pre[s0 + 1] = excl + c0;
+    if (threadIdx.x == RUN_BLOCK - 1) pre[NSEG] = v;
+  }
+  __syncthreads();
+  // a workgroup past every listed chunk (the grid covers n envs, a uniform step lists ~1 in 5;
+  // the options' padding adds < 64 each) leaves before it stages the level: ~3/4 of the grid
+  if ((int)(blockIdx.x * RUN_BLOCK) >= pre[NSEG] + NLIST * 63) {
+    kst_end(ks, kt0);
+    return;
+  }
+  if (threadIdx.x == 0) {
+    int acc = 0;
+    for (int j = 0; j < NLIST; ++j) {
+      const int sb = j * WSHARDS, se = sb + WSHARDS;
+      ostart[j] = acc;
+      oraw[j] = pre[sb];
+      acc += (pre[se] - pre[sb] + 63) & ~63;
+    }
+    ostart[NLIST] = acc;
+    oraw[NLIST] = pre[NSEG];
+  }
+  RUN_LEVEL_IN_LDS();  // includes the barrier (ostart / oraw)
+  const int total = ostart[NLIST];
+  const int base = (blockIdx.x * RUN_BLOCK + threadIdx.x) & ~63;  // wave w runs chunk w
+  int oj = 0;  // ostart[oj] <= base < ostart[oj + 1] (wave-uniform)
+  while (oj + 1 < NLIST && ostart[oj + 1] <= base) ++oj;
+  oj = __builtin_amdgcn_readfirstlane(oj);
+  const int k = kOrder[oj];
+  // this lane's place in option k's lists (the raw prefix's coordinates), and its segment
+  const int qraw = oraw[oj] + base + (threadIdx.x & 63) - ostart[oj];
+  const bool live = base < total && qraw < oraw[oj + 1];
+  int seg = oj * WSHARDS;
+  if (live) {
+    int hi = seg + WSHARDS;  // pre[seg] <= qraw < pre[hi]
+    while (hi - seg > 1) {
+      const int mid = (seg + hi) >> 1;
+      if (pre[mid] <= qraw) seg = mid; else hi = mid;
+    }
+  }
+  const int idx = qraw - pre[seg];
+  int64_t i = 0;
+  StepResult r{0, 0, 0, 0};
+  Env e;
+  e.mti = 0u;
+  int2 ep = make_int2(0, 0);
+  uint32_t draws = 0;
+  int regens = 0;  // wave-uniform
+  int lregen = 0;  // halves this lane regenerated in its option loop
+  lds_u8* const wscr = (lds_u8*)win + (threadIdx.x >> 6) * WIN_WAVE_BYTES;
+  unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0;
+  TG_STAMP(t0);
+#ifdef TG_DIAG_STAMPS
+  const unsigned long long rt0 = __builtin_amdgcn_s_memrealtime();
+#endif
+  (void)t0; (void)t1; (void)t2; (void)t3;
+#ifdef TG_DIAG_STAMPS
+  unsigned long long ph1 = 0, ph2 = 0, ph3 = 0;
+  uint32_t prounds = 0;
+#endif
+  if (live) {
+    const int64_t at = (int64_t)seg * w.shard_cap + idx;
+    i = w.lists[at];
+    unpack(w.wst4[at], w.wang[at], e);
+    ep = w.wep[at];
+    RngCodes rng(S.mt + i * MT_STORE, S.mc + i * MT_CODES, e.mti, wscr);
+    rng.prime();  // issue the code loads now; the first draw comes after the policy setup
+    TG_STAMP(t1);
+    if (k != O_GO_LEFT && k != O_GO_RIGHT && k != O_INTERACT) __builtin_amdgcn_s_setprio(PRIO_SLOW);
+    // k is wave-uniform: one specialised loop; L_RESET's envs run none (reward None)
+    if (k != L_RESET) run_option(L, trig, m, e, k, rng, r);
+    TG_STAMP(t2);
+#ifdef TG_DIAG_STAMPS
+    ph1 = rng.ph[1], ph2 = rng.ph[2], ph3 = rng.ph[3], prounds = rng.rounds;
+#endif
+    r.done = is_done(e);
+    finish_step<AUTORESET, FINAL, false>(level_div(L), e, rng, i, r, ep, io);  // valid: k_classify's
+    e.mti = rng.finish();  // a half left here: MT_STALE, listed by the next k_classify
+    draws = rng.draws;
+    lregen = (int)rng.regens;
+    if (e.f & E_MASK) atomicOr(err_or, e.f & E_MASK);
+  }
+  // (k_run's grid has BLOCK / RUN_BLOCK workgroups per stats slot, as wave_stats below)
+  if (AUTORESET)
+    record_episodes(live && r.done, g0 + i, ep, io.tstep, q, stats, (int64_t)blockIdx.x / (BLOCK / RUN_BLOCK));
+  if (live) {
+    S.st4[i] = pack(e);
+    S.ang[i] = make_double2(e.ang0, e.ang1);
+    S.ep[i] = ep;
+  }
+  __builtin_amdgcn_s_setprio(0);
+  wave_stats(stats, 0, 0, r.ticks, (int)draws, AUTORESET ? (live && r.done) : 0,
+             regens + (__ballot(lregen != 0) ? wave_sum(lregen) : 0), true,
+             (int64_t)blockIdx.x / (BLOCK / RUN_BLOCK));
+  kst_end(ks, kt0);
+#ifdef TG_DIAG_STAMPS
+  TG_STAMP(t3);
+  {
+    int mx = r.ticks;
+    for (int o = 32; o > 0; o >>= 1) mx = max(mx, __shfl_xor(mx, o, 64));
+    const int sum = wave_sum(r.ticks);
+    const unsigned long long bl = __ballot(live);
+    const int src = bl ? __ffsll((long long)bl) - 1 : 0;
+    const unsigned long long a1 = __shfl(t1, src, 64);
+    const unsigned long long a2 = __shfl(t2, src, 64);
+    const int wv = (blockIdx.x * RUN_BLOCK + threadIdx.x) >> 6;
+    const unsigned long long rt3 = __builtin_amdgcn_s_memrealtime();
+    // the phases of the lane whose option loop ran longest (the wave's own time)
+    int lmax = src;
+    unsigned long long best = 0;
+    for (int l = 0; l < 64; ++l) {
+      const unsigned long long tl = __shfl(ph1 + ph2 + ph3, l, 64);
+      if (((bl >> l) & 1ull) && tl > best) best = tl, lmax = l;
+    }
+    const unsigned long long p1 = __shfl(ph1, lmax, 64), p2 = __shfl(ph2, lmax, 64),
+                             p3 = __shfl(ph3, lmax, 64);
+    const uint32_t pr = __shfl(prounds, lmax, 64);
+    if ((threadIdx.x & 63) == 0 && wv < NSTAMP_WAVES) {
+      unsigned long long* const g = g_stamps + (size_t)wv * NSTAMP;
+      // an idle wave (no listed chunk) is option 15 with 1 iteration
+      g[0] = bl ? a1 - t0 : 0;
+      g[1] = bl ? a2 - a1 : 0;
+      g[2] = bl ? t3 - a2 : t3 - t0;
+      g[3] = bl ? (unsigned long long)mx | ((unsigned long long)sum << 32) | ((unsigned long long)k << 56)
+                : 1ull | (15ull << 56);
+      g[4] = rt0;
+      g[5] = rt3;
+      g[6] = p1;
+      g[7] = p2;
+      g[8] = p3;
+      g[9] = pr;
+      g[10] = (unsigned long long)regens;  // halves this wave regenerated from the queue
+    }
+  }
+#endif
+}
+
+// ---- deferred regeneration of the listed stale MT halves (k_regen) ----------------------------
+// k_classify appends the halves the previous step left stale (MT_STALE) to its shard's refill
+// list and marks them MT_LISTED; every REGEN_STEPS compact steps (and on tg_regenerate) k_regen
+// regenerates every pending entry with a full-occupancy grid and no option loops beside it: the
+// waves of XCD x (blockIdx.x % 8) take list x's entries, an even share each (the halves cost
+// the same: MT_HALF_GENS twists), the rest from the list's counter.  An entry is regenerated iff
+// its env's state word still says MT_STALE (its lane may have regenerated the half itself, or
+// crossed again since): the half not holding the position, from the last generation of the one
+// holding it.  The word loses MT_STALE | MT_LISTED by an atomic AND before the twist (the
+// claim: of several entries for one env, one regenerates).  It runs alone on the stream, so
+// nothing else touches the state meanwhile.
+// Slack: a listed half is needed again only after the env consumes the rest of the half it is
+// in, >= MT_HALF / 2 - (one step's draws) ~ 2,400 draws, more than REGEN_STEPS steps draw on the
+// default level (<= ~110 per step); a lane that gets there first regenerates the half itself.
+// k_regen's ring stores: non-temporal (its words and codes are read steps later, not by this
+// launch) with TG_REGEN_NT=1
+#ifndef TG_REGEN_NT
+#define TG_REGEN_NT 0
+#endif
+constexpr bool REGEN_NT = TG_REGEN_NT != 0;
+__global__ __launch_bounds__(BLOCK) void k_regen(Soa S, const uint32_t* __restrict__ refill,
+                                                 int64_t rcap, int32_t* __restrict__ ctr,
+                                                 int32_t* __restrict__ ctr_next,
+                                                 unsigned long long* __restrict__ stats,
+                                                 int nstat, unsigned long long* __restrict__ ks) {
+  const unsigned long long kt0 = kst_begin(ks);
+  __shared__ __attribute__((aligned(16))) uint32_t scratch[BLOCK / 64][MT_N];
+  lds_u32* const scr = (lds_u32*)scratch[threadIdx.x >> 6];
+  const int lane = threadIdx.x & 63;
+  const int xcd = (int)(blockIdx.x & 7u);
+  const int64_t cnt = ctr[(RCTR_LIST + xcd) * CTR_STRIDE];
+  if (blockIdx.x == 0 && threadIdx.x < RCTR_N) ctr_next[threadIdx.x * CTR_STRIDE] = 0;
+  int32_t* const q = ctr + xcd * CTR_STRIDE;
+  const uint32_t* const list = refill + xcd * rcap;
+  uint32_t* const st_w = reinterpret_cast<uint32_t*>(S.st4);  // word 4i + 3: env i's MT word
+  auto src_of = [&](uint32_t env, uint32_t s) {
+    const uint32_t dst = (uint32_t)MT_HALF - mt_half(s & MT_POS_MASK);
+    return (const glb_u32*)(S.mt + (int64_t)env * MT_STORE + regen_src_off(dst));
+  };
+  // this wave's index among its XCD's waves; the first grab is static (an even share, at most
+  // 64: one entry per lane), the rest come from the counter, which starts past the static ones
+  const int wx = (int)(blockIdx.x >> 3) * (BLOCK / 64) + (int)(threadIdx.x >> 6);
+  const int64_t nwx = (int64_t)((gridDim.x - (unsigned)xcd + 7u) >> 3) * (BLOCK / 64);
+  int64_t grab = (cnt + nwx - 1) / nwx;
+  if (grab > 64) grab = 64;
+  if (grab < 1) grab = 1;
+  int halves = 0;
+  bool first = true;
+  while (true) {
+    int64_t j0 = (int64_t)wx * grab;
+    if (!first) {
+      int g = 0;
+      if (lane == 0) g = atomicAdd(q, (int)grab);
+      j0 = nwx * grab + __builtin_amdgcn_readfirstlane(g);
+    }
+    first = false;
+    if (j0 >= cnt) break;
+    const int64_t m = cnt - j0 < grab ? cnt - j0 : grab;
+    const uint32_t env_l = lane < m ? list[j0 + lane] & 0x7FFFFFFFu : 0u;
+    // claim: clear MT_STALE | MT_LISTED and regenerate only if this lane's clear found
+    // MT_STALE.  An env can be listed twice before a drain (its lane regenerated the listed
+    // half itself, crossed again, and the next k_classify listed the new stale half): both
+    // entries name the half not holding the position, and the second claim finds it clean
+    // (round 4 regenerated such a half once per entry: 20,320 vs 15,360 halves on the corridor
+    // level).  Entries of one grab for one env are serialised at the word's L2 channel.
+    const uint32_t st_l = lane < m ? atomicAnd(&st_w[(int64_t)env_l * 4 + 3], ~(MT_STALE | MT_LISTED)) : 0u;
+    unsigned long long need = __ballot(lane < m && (st_l & MT_STALE));
+    // one half at a time: 52 VGPRs, 8 waves per SIMD (the next half's source loads pipelined
+    // into this one's twist took 76 VGPRs, 6 waves, and measured no faster: DESIGN.md §3.3)
+    while (need) {
+      const int L = __ffsll((long long)need) - 1;
+      need &= need - 1;
+      const uint32_t env = __builtin_amdgcn_readlane(env_l, L), s = __builtin_amdgcn_readlane(st_l, L);
+      const uint32_t dst = (uint32_t)MT_HALF - mt_half(s & MT_POS_MASK);
+      TwistIn t;
+      twist_load(src_of(env, s), t);
+      twist_chain<REGEN_NT>(t, (glb_u32*)(S.mt + (int64_t)env * MT_STORE), S.mc + (int64_t)env * MT_CODES,
+                            (int)(dst / (uint32_t)MT_N), MT_HALF_GENS, true, scr);
+      ++halves;
+    }
+  }
+  // the grid can exceed the stats slots (>= 8 workgroups, one per XCD counter, at small n)
+  if (lane == 0 && halves)
+    atomicAdd(&stats[(size_t)(blockIdx.x % (unsigned)nstat) * ST_COUNT + ST_REGENS],
+              (unsigned long long)halves);
+  kst_end(ks, kt0);
+}
+
+// ---- TG_MODE_FLOW's helpers (tg_flow.h; k_flow itself is tg_flow.hip's) -----------------------
+// the XCC ids the device's workgroups run on (one bit each): the flow's sub-problems
+__global__ void k_census(uint32_t* mask) {
+  if (threadIdx.x == 0) atomicOr(mask, 1u << (xcc_id() & 31u));
+}
+// after every k_flow launch, on its stream (one wave): a sub-problem whose chunks did not all
+// finish step K - 1 sets TG_ERR_FLOW (no wave ran on its XCD; tg_flow.h "Coherence")
+__global__ void k_flow_check(const int32_t* __restrict__ ctl, int P, int32_t C,
+                             uint32_t* __restrict__ err_or) {
+  const int x = (int)threadIdx.x;
+  if (x < P) {
+    const int Cx = (C - x + P - 1) / P;
+    if (Cx > 0 && ctl[(int64_t)x * CTL_WORDS + FC_FIN * FC_STRIDE] != Cx) atomicOr(err_or, E_FLOW);
+  }
+}
+
+// ---- per-env queries ----------------------------------------------------------------------
+__global__ __launch_bounds__(BLOCK) void k_mask(Soa S, int64_t n, Level L,
+                                                 const uint32_t* __restrict__ grid,
+                                                 uint16_t* __restrict__ out) {
+  LEVEL_IN_LDS();
+  (void)trig;
+  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= n) return;
+  Env e;
+  unpack(S.st4[i], S.ang[i], e);
+  out[i] = (uint16_t)available_mask(L, m, e);
+}
+
+__global__ __launch_bounds__(BLOCK) void k_observe(Soa S, int64_t n, Level L,
+                                                    double* __restrict__ obs) {
+  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= n) return;
+  Env e;
+  unpack(S.st4[i], S.ang[i], e);
+  double o[9];
+  observe(L, e, o);
+  store_obs(obs, i, o);
+}
+
+// a[t, g] = h(a0, g, t) % 9, or the k-th set bit of available_mask (masked-uniform)
+__global__ __launch_bounds__(BLOCK) void k_actions(Soa S, int64_t n, Level L,
+                                                    const uint32_t* __restrict__ grid,
+                                                    uint64_t a0, int64_t g0, int64_t t,
+                                                    int policy, int32_t* __restrict__ out) {
+  __shared__ LdsLevel lv;
+  if (policy == TG_POLICY_MASKED) stage_level(lv, grid, L);  // uniform branch
+  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const Map m{reinterpret_cast<const uint8_t*>(lv.grid), L.W, L.H};
+  Env e{};
+  if (policy == TG_POLICY_MASKED) unpack(S.st4[i], S.ang[i], e);
+  out[i] = policy_action(L, m, e, policy, a0, g0 + i, t);
+}
+
+// The learned actor (tg_policy_mlp.h): one env per lane.  The lane forms its obs row
+// as k_observe does and keeps x, the first layer's activations and the ten head accumulators in
+// VGPRs; the packed parameters sit at a wave-uniform address, so every weight is a scalar load
+// into an SGPR operand of a v_fma_f32 (nothing is written through the scalar path).  masked: the
+// level is staged as k_actions stages it and A is available_mask's bits.  Writes actions and,
+// where given, logp, value and logits [n][9] of envs [0, n) of the view S (g0: env 0's GLOBAL
+// index).  No atomics: two launches on the same state give identical bits.
+template <int H, int ACT>
+__global__ __launch_bounds__(BLOCK) void k_policy_mlp(Soa S, int64_t n, Level L,
+                                                       const uint32_t* __restrict__ grid,
+                                                       const float* __restrict__ params, int masked,
+                                                       int mode, uint64_t a0, int64_t g0, int64_t t,
+                                                       int32_t* __restrict__ actions,
+                                                       float* __restrict__ logp,
+                                                       float* __restrict__ value,
+                                                       float* __restrict__ logits) {
+  __shared__ LdsLevel lv;
+  if (masked) stage_level(lv, grid, L);  // uniform branch
+  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const Map m{reinterpret_cast<const uint8_t*>(lv.grid), L.W, L.H};
+  Env e;
+  unpack(S.st4[i], S.ang[i], e);
+  double o[9];
+  observe(L, e, o);
+  float lg[MLP_OUT], v;
+  mlp_forward<H, ACT>(params, o, lg, v);
+  const uint32_t allowed = mlp_allowed(masked, masked ? available_mask(L, m, e) : 0u);
+  float lp;
+  actions[i] = mlp_select(lg, allowed, mode, mlp_uniform(a0, g0 + i, t), lp);
+  if (logp) logp[i] = lp;
+  if (value) value[i] = v;
+  if (logits) {
+    float* q = logits + i * MLP_OUT;
+#pragma unroll
+    for (int k = 0; k < MLP_OUT; ++k) q[k] = lg[k];
+  }
+}
+
+// move up to `cap` completed-episode records to `out`, keep the rest queued (device only,
+// so the per-step episode gather never waits on the host)
+__global__ __launch_bounds__(BLOCK) void k_drain_episodes(tg_episode* __restrict__ eps,
+                                                           int32_t* eps_count, int32_t eps_cap,
+                                                           tg_episode* __restrict__ out,
+                                                           int32_t* __restrict__ count,
+                                                           int32_t cap) {
+  int32_t n = *eps_count;
+  if ((uint32_t)n > (uint32_t)eps_cap) n = eps_cap;  // see record_episodes: never above cap + n
+  const int32_t m = n < cap ? n : cap;
+  for (int32_t k = threadIdx.x; k < m; k += BLOCK) out[k] = eps[k];
+  __syncthreads();
+  for (int32_t base = m; base < n; base += BLOCK) {  // shift the remainder down in chunks
+    const int32_t k = base + threadIdx.x;
+    tg_episode r;
+    if (k < n) r = eps[k];
+    __syncthreads();
+    if (k < n) eps[k - m] = r;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    *eps_count = n - m;
+    *count = m;
+  }
+}
+
+// The six collision predicates (IM/:232-288) at every pixel of [x0, x1) x [y0, y1) with the
+// doors closed per door_bits, bit order as the reference's predicate listing: up_clear, can_go_up,
+// can_go_down, can_go_left, can_go_right, can_fall.  The device build of Map (mul24 / div48
+// take the __umul24 path only here), pinned against the reference's F2 truth tables.
+__global__ __launch_bounds__(BLOCK) void k_predicates(Level L, const uint32_t* __restrict__ grid,
+                                                       int x0, int x1, int y0, int y1,
+                                                       uint32_t door_bits,
+                                                       uint8_t* __restrict__ out) {
+  LEVEL_IN_LDS();
+  (void)trig;
+  const int64_t w = x1 - x0;
+  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= w * (int64_t)(y1 - y0)) return;
+  Env e{};
+  e.px = x0 + (int)(i % w);
+  e.py = y0 + (int)(i / w);
+  e.f = (door_bits & 7u) << F_OBJ;
+  out[i] = (uint8_t)((unsigned)m.up_clear(e) | (unsigned)m.can_go_up(e) << 1 |
+                     (unsigned)m.can_go_down(e) << 2 | (unsigned)m.can_go_side(e, -1) << 3 |
+                     (unsigned)m.can_go_side(e, +1) << 4 | (unsigned)m.can_fall(e) << 5);
+}
+
+// tg_read_state's MT part: the generation holding each env's position (CPython's mt[]),
+// envs [first, first + count) -> dst [count][624] (contiguous), 4 words per lane (an odd
+// generation's twisted from the stored one before it)
+__global__ __launch_bounds__(BLOCK) void k_gather_mt(Soa S, int64_t first, int64_t count,
+                                                      uint32_t* __restrict__ dst) {
+  constexpr int Q = MT_N / 4;  // 156 uint4 per generation
+  const int64_t t = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (t >= count * Q) return;
+  const int64_t k = t / Q;
+  const int q = (int)(t - k * Q);
+  const int64_t i = first + k;
+  const uint32_t g = (S.st4[i].w & MT_POS_MASK) / (uint32_t)MT_N;
+  const uint32_t* const mt = S.mt + i * MT_STORE;
+  uint4 v;
+  if (g & 1u) {
+    const uint32_t* const prev = mt + mt_store_off(g - 1u);
+    v = make_uint4(twist_at(prev, 4 * q), twist_at(prev, 4 * q + 1), twist_at(prev, 4 * q + 2),
+                   twist_at(prev, 4 * q + 3));
+  } else {
+    v = reinterpret_cast<const uint4*>(mt + mt_store_off(g))[q];
+  }
+  reinterpret_cast<uint4*>(dst)[t] = v;
+}
+
+// tg_probe_dispatch: nothing (a dependent kernel boundary's cost alone)
+__global__ __launch_bounds__(BLOCK) void k_null() {}
+
+__global__ __launch_bounds__(BLOCK) void k_errors(const uint4* __restrict__ st4, int64_t n,
+                                                   uint32_t* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  const uint32_t f = i < n ? (st4[i].y & E_MASK) : 0u;
+  if (f) atomicOr(out, f);
+}
+
+}  // namespace

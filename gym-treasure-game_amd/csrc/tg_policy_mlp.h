@@ -1,5 +1,5 @@
 // tg_policy_mlp.h — the learned actor's arithmetic (tg_policy_mlp / tg_rollout_mlp of
-// include/tg_amd.h), one env at a time.  Shared by k_policy_mlp (tg_amd.hip) and by
+// include/tg_amd.h), one env at a time.  Shared by k_policy_mlp (tg_kernels.h) and by
 // the host-only check build (tests/native_policy, plain g++): needs <math.h> only.
 //
 // Everything is f32 and every multiply-add is an explicit fmaf in a fixed order (the build has

@@ -3,7 +3,7 @@
 // chained in the wave's LDS scratch, every generation's 312 draw codes and the even
 // generations' 624 words stored (tg_core.h MT_STORE).
 // Used by k_regen (the deferred regeneration, every 16 compact steps), k_gen_twist (tg_create,
-// tg_write_state), k_reset and k_step (tg_amd.hip).  (The twist variants measured in isolation,
+// tg_write_state), k_reset (tg_kernels.h) and k_step (step_env, tg_dev.h).  (The twist variants measured in isolation,
 // DESIGN.md §3.3, are restated in scripts/calib/twist_bench.hip.)
 //
 // What bounds it: not HBM.  One generation is ~2.8 KB of stores, and the

@@ -4,7 +4,7 @@
 // pattern k_run issues.  Every buffer is 1 GiB or more (past the 256 MiB Infinity Cache), and
 // every kernel requests a known number of bytes, printed with its name; run it under
 //   rocprofv3 --pmc FETCH_SIZE -- ./calib_fetch     and     rocprofv3 --pmc WRITE_SIZE -- ...
-// and divide.  The patterns (tg_amd.hip):
+// and divide.  The patterns (tg_twist.h, tg_dev.h):
 //   dword      the twist's loads / stores: lane p reads word p of a 624-word generation, 64
 //              lanes = 256 contiguous bytes per instruction (twist_load / twist_store)
 //   x4         16 B per lane, contiguous across the wave (k_classify / the worklist records)

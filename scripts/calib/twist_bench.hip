@@ -1,5 +1,5 @@
 // twist_bench.hip — DIAGNOSTIC (not the product): throughput of the whole-wave MT19937
-// regeneration ("twist", tg_amd.hip twist_load / twist_store) in isolation, in variants, over a
+// regeneration ("twist", tg_twist.h twist_load / twist_store) in isolation, in variants, over a
 // k_run-sized list of stale halves (random envs of a 1M-env batch, as the refill queue sees
 // them).  Every variant's output (words and draw codes) is checked against variant A's.
 //   A  words in VGPRs (24 loads per lane), one twist at a time      (k_gen_twist, round 2)
@@ -222,7 +222,7 @@ __device__ __forceinline__ void chain2(lds_u32* s, uint32_t* dst, uint8_t* dst_c
   }
 }
 
-// the product's grouped in-place twist (tg_amd.hip twist_lds), with parts switched off
+// the product's grouped in-place twist (tg_twist.h twist_lds), with parts switched off
 __device__ __forceinline__ void codes_top27(lds_u32* nw, uint8_t* dst_c) {
   const int lane = threadIdx.x & 63;
 #pragma unroll

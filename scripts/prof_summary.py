@@ -28,7 +28,7 @@ from collections import defaultdict
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MT_HALF_GENS = 8  # tg_core.h: generations per half of an env's MT ring
-REGEN_STEPS = 16  # tg_amd.hip: steps per k_regen launch
+REGEN_STEPS = 16  # tg_dev.h: steps per k_regen launch
 
 
 def short(name):
@@ -139,7 +139,7 @@ def main():
     # the step's kernels: k_classify + k_run (compact) or k_step (direct)
     names = (("k_classify", "k_run", "k_regen") if a.mode == "compact" else ("k_step",))
     # k_regen drains REGEN_STEPS steps' refill lists per launch: its per-step share
-    spl = 16.0  # tg_amd.hip REGEN_STEPS: steps per k_regen launch at steady state
+    spl = 16.0  # tg_dev.h REGEN_STEPS: steps per k_regen launch at steady state
     step_k = [k for k in pm if k.split("<")[0] in names]
     if step_k and all("FETCH_SIZE" in pm[k] for k in step_k):
         known = 16.0 * a.envs  # k_errors: one 16-B uint4 per env, 16 B per lane

@@ -143,7 +143,7 @@ int main(int argc, char** argv) {
   const int runpct = argc > 5 ? atoi(argv[5]) : 21;  // env-steps that run an option (%)
   C = (N + 63) / 64;
   const int cxm = (C + P - 1) / P;
-  lcap = cxm * 64; jcap = cxm + 1; qcap = KMAX * (2 * cxm + NLIST);  // as tg_amd.hip flow_init
+  lcap = cxm * 64; jcap = cxm + 1; qcap = KMAX * (2 * cxm + NLIST);  // as flow_init (tg_amd.hip)
   outst = std::vector<std::atomic<int>>(C);
   ccount = std::vector<std::atomic<int>>((size_t)C * K);
   rcount = std::vector<std::atomic<int>>((size_t)N * K);

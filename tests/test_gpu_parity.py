@@ -466,6 +466,51 @@ def test_rollout_equals_step_loop_and_oracle(tg, oracle, mode, policy):
     b.close()
 
 
+_SELECTION_REFS = {}
+
+
+def selection_ref(oracle, masked, ar):
+    """the oracle's run for test_every_step_kernel_selection, computed once per (policy, reset)"""
+    if (masked, ar) not in _SELECTION_REFS:
+        _SELECTION_REFS[(masked, ar)] = oracle.run(21, 0, 300, 40, 0xC0DE, masked, bool(ar))
+    return _SELECTION_REFS[(masked, ar)]
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("masked", [0, 1])
+@pytest.mark.parametrize("ar,fo,given", [(0, 0, 1), (0, 1, 1), (1, 0, 1), (1, 1, 1),
+                                         (0, 0, 0), (1, 0, 0)])
+def test_every_step_kernel_selection(tg, oracle, mode, masked, ar, fo, given):
+    """The step kernels are instantiated per (auto-reset, a final_obs output, policy: actions
+    given, or uniform / masked evaluated in the step) and the host picks one per launch.  Every
+    selection an entry point can make (tg_rollout passes no final_obs, so the policies evaluated
+    in the step have none), in both modes, against the oracle bit for bit: 300 envs (two
+    workgroups, a partial last wave), 40 steps."""
+    n, steps, a0 = 300, 40, 0xC0DE
+    pol = "masked" if masked else "uniform"
+    ref = selection_ref(oracle, masked, ar)
+    vec = tg.TreasureGameVec(n, seed=21, autoreset=bool(fo), mode=mode)  # fo: final rows allocated
+    vec.autoreset = bool(ar)
+    vec.reset()
+    if given:
+        rows = {k: [] for k in ("obs", "reward", "valid", "done", "final_obs")}
+        for t in range(steps):
+            o, r, v, d, _ = vec.step(vec.policy_actions(t, a0, pol))
+            for k, x in zip(("obs", "reward", "valid", "done"), (o, r, v, d)):
+                rows[k].append(x.cpu().numpy())
+            if fo:
+                rows["final_obs"].append(vec._final.cpu().numpy())
+        got = {k: np.stack(x, 1) for k, x in rows.items() if x}
+    else:
+        out = vec.rollout(steps, t0=0, action_seed=a0, policy=pol)
+        got = {k: np.ascontiguousarray(np.moveaxis(out[k].cpu().numpy(), 0, 1))
+               for k in ("obs", "reward", "valid", "done")}
+    for k in got:  # (auto-reset off: the oracle's final rows are its obs rows)
+        assert_bits(got[k], ref[k][:, 1:], k)
+    assert vec.errors() == 0
+    vec.close()
+
+
 LEVELS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "levels")
 
 
