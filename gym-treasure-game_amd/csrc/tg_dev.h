@@ -309,7 +309,12 @@ struct RngCodesT {
       sync();
       fill();
     }
-    if (!loaded) {  // the window's DMAs must have landed
+    land();
+  }
+  // the window's DMAs have landed (they are in flight only between a fill and this call); the
+  // first draw's code is read ahead
+  __device__ __forceinline__ void land() {
+    if (!loaded) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       nxc = read();
       loaded = true;
@@ -322,39 +327,14 @@ struct RngCodesT {
     return *reinterpret_cast<const lds_u32*>(cell + (4u * d / WIN_UNIT) * WIN_SLOT_BYTES +
                                              (4u * d) % WIN_UNIT);
   }
-  // walk_ticks (tg_core.h) four draws per LDS read: the codes of a dword are applied one by one
-  // (each tick checks the span, the staged draws and the cap at its start, as walk_ticks), so
-  // the result is walk_ticks's; the next dword is read while this one is applied
+  // walk_ticks (tg_core.h) by multi-draw hops (walk_hops there: whole code dwords while all
+  // four of their ticks are plain, the dword the walk ends in tick by tick), with walk_ticks's
+  // result
   template <int DIR>
   __device__ __forceinline__ int walk(int& x, const int lim, const int cap) {
-    int taken = 0;
-    if (!((DIR > 0 ? x <= lim : x >= lim) && left >= TICK_DRAWS && cap > 0)) return 0;
-    uint32_t w = dword(rd >> 2);
-    while (true) {
-      const uint32_t wn = dword((rd >> 2) + 1u);  // inside the window: left >= TICK_DRAWS here
-      const int k = (int)(rd & 3u);
-      int moved = 0;
-      bool act = true;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int st = code_step((w >> (8 * i)) & 0xFFu, DIR < 0);
-        act = act && (i >= k ? ((DIR > 0 ? x <= lim : x >= lim) &&
-                                left - (uint32_t)moved >= TICK_DRAWS && taken + moved < cap)
-                             : true);
-        if (i >= k && act) {
-          x += st;
-          ++moved;
-        }
-      }
-      taken += moved;
-      rd += (uint32_t)moved;
-      left -= (uint32_t)moved;
-      n += (uint32_t)moved;
-      draws += (uint32_t)moved;
-      if (moved < 4 - k) break;  // the walk stopped inside this dword
-      if (!((DIR > 0 ? x <= lim : x >= lim) && left >= TICK_DRAWS && taken < cap)) break;
-      w = wn;
-    }
+    const int taken = walk_hops<DIR>(*this, x, lim, cap);
+    n += (uint32_t)taken;
+    draws += (uint32_t)taken;
     nxc = read();  // code() reads one draw ahead
     return taken;
   }
@@ -395,11 +375,23 @@ struct RngCodesT {
     return mt_double(w.w0, w.w1);
   }
   __device__ __forceinline__ double uniform(double a, double b) { return a + (b - a) * random(); }
+  // the window's DMAs have landed (the step's epilogue calls it before its first result store:
+  // stores count in vmcnt too, so a wait placed after them is a wait for their acknowledgement)
+  __device__ __forceinline__ void drain() {
+    if (primed) land();
+  }
   // drain the DMAs (the window is reused as scratch); returns the state word to store: the
   // entry's stale half, still stale, keeps its bits (listed or not); a half left in this launch
-  // is stale and not listed yet; none, if the lane regenerated the stale half itself
+  // is stale and not listed yet; none, if the lane regenerated the stale half itself.
+  // The per-step kernels call drain() before their first result store, so nothing is in flight
+  // here and no wait stands behind those stores; a caller that did not (k_reset) still lands
+  // its window.  k_flow keeps the unconditional wait it had.
   __device__ __forceinline__ uint32_t finish() {
-    if (primed) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    if constexpr (FLOW) {
+      if (primed) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    } else {
+      drain();
+    }
     sync();
     primed = loaded = false;
     return pos | (stale == NONE ? 0u : entered ? MT_STALE : tag);
@@ -686,6 +678,7 @@ __device__ __forceinline__ StepResult step_env(const Soa& S, int64_t n, const Le
       act = io.actions[i];
     }
     r = env_step(L, trig, m, e, act, rng);
+    rng.drain();  // before the first result store (RngCodes::finish)
     finish_step<AUTORESET, FINAL>(level_div(L), e, rng, i, r, ep, io);
     e.mti = rng.finish();
     draws = rng.draws;

@@ -397,6 +397,7 @@ __global__ __launch_bounds__(RUN_BLOCK) void k_run(Soa S, int64_t n, Level L,
     ph1 = rng.ph[1], ph2 = rng.ph[2], ph3 = rng.ph[3], prounds = rng.rounds;
 #endif
     r.done = is_done(e);
+    rng.drain();  // before the first result store: no wait for the window stands behind them
     finish_step<AUTORESET, FINAL, false>(level_div(L), e, rng, i, r, ep, io);  // valid: k_classify's
     e.mti = rng.finish();  // a half left here: MT_STALE, listed by the next k_classify
     draws = rng.draws;
