@@ -1577,40 +1577,58 @@ TG_HD int ladder_tick(const Level& L, const Map& m, const LadMasks& lm, Env& e, 
   return -1;  // STEP_REWARD
 }
 
-// The ladder options' while-not-done loop (OP/:28-31): a plain phase (ladder_plain_limit's
-// span; one draw and py += noisy per tick, as the full tick there), then one full tick, which
-// may open the next span.  One loop for both probe forms (two copies of the
-// plain-tick / full-tick / TICK_CAP control flow): `pr` gives the span's predicates (cell probes
-// or the level bitmasks), `full()` the full tick (policy<K> + tick<>, or ladder_tick).  The
-// plain phase is the go loop's walk (rng.walk: multi-draw hops on the device).  (The earlier
-// batched walk, each dword's codes applied one by one, took k_run from 82 to 98 VGPRs here: 4
-// instead of 5 waves per SIMD; with walk_hops k_run stays at 5.)
-template <int DIR, class R, class P, class Full>
-TG_HD void ladder_loop(const Level& L, const Map& m, Env& e, Opt& o, R& rng, StepResult& r,
-                       const P& pr, Full full) {
+// One full tick of an option's while-not-done loop (OP/:28-31), counted: the staged draws
+// restocked (rng.reserve: the one refill site of every loop), the tick itself (`full()` runs it
+// and yields its reward), then the tick count against TICK_CAP (E_TICKCAP).  Returns whether the
+// loop may go on.  rng.phase marks the segments for the diagnostic build's per-phase clock
+// (tg_run_diag.h): up to 1 the plain walk, up to 2 the refill, up to 3 the full tick.
+// (k_run's register allocation is sensitive to the form of this helper and of span_loop's loop
+// condition: with `full` taken by value, or with `if (!counted_tick(..)) break; } while (!o.done)`
+// there, the ladder loops took k_run from 92-94 to 109-110 VGPRs, 4 instead of 5 waves per SIMD.
+// Compare the kernels' resource usage after an edit here.)
+template <class R, class Full>
+TG_HD bool counted_tick(Env& e, R& rng, StepResult& r, uint32_t draws, const Full& full) {
+  rng.phase(1);
+  rng.reserve(draws);
+  rng.phase(2);
+  r.reward += full();
+  rng.phase(3);
+  if (++r.ticks < TICK_CAP) return true;
+  e.f |= E_TICKCAP;
+  return false;
+}
+
+// The go and ladder options' loop along one axis (`x`: e.px or e.py).  Two phases per round.
+// Plain phase: every lane inside its span (go_plain_limit / ladder_plain_limit) takes plain
+// ticks, one draw and x += noisy each, as the full tick there, until it leaves the span.  Full
+// phase: then no lane of the wave is in a span, and each takes one full tick, `full(lim)`, which
+// yields the tick's reward and, when the option goes on, the next span's limit.  Each lane's own
+// tick sequence is the reference's; only the interleaving across lanes differs, and the full
+// tick's code runs once per round.  FACE: a run of plain ticks sets the facing bit (go).
+// The plain phase is per lane: a lane leaves when its span ends, the wave when all have (a
+// ballot-driven loop, with the idle lanes kept inside, made the compiler copy ~26 loop-carried
+// registers per iteration and was slower).  It also ends when the staged draws run low: the full
+// tick restocks them in rng.reserve, so the plain loop's body holds no refill code.  It is
+// rng.walk: multi-draw hops on the device.  (The earlier batched walk, each dword's codes
+// applied one by one, took k_run from 82 to 98 VGPRs on the ladders: 4 instead of 5 waves per
+// SIMD; with walk_hops k_run stays at 5.)
+template <int DIR, bool FACE, class R, class Full>
+TG_HD void span_loop(const Level& L, Env& e, int& x, const Opt& o, R& rng, StepResult& r,
+                     const Full& full) {
   int lim = DIR > 0 ? -0x40000000 : 0x40000000;  // no plain tick before the first full one
   do {
     rng.phase(0);
-    if (const int t = rng.template walk<DIR>(e.py, lim, TICK_CAP - r.ticks)) {  // plain ticks
+    if (const int t = rng.template walk<DIR>(x, lim, TICK_CAP - r.ticks)) {  // plain ticks
+      if (FACE) e.f = DIR > 0 ? (e.f | F_FACING) : (e.f & ~F_FACING);
       r.reward -= t;
       r.ticks += t;
-      if (DIR > 0 ? e.py > lim : e.py < lim) pickups(L, e);  // left the span: as the full tick
+      if (DIR > 0 ? x > lim : x < lim) pickups(L, e);  // left the span: as the full tick
       if (r.ticks >= TICK_CAP) {
         e.f |= E_TICKCAP;
         break;
       }
     }
-    rng.phase(1);
-    rng.reserve(TICK_DRAWS);
-    rng.phase(2);
-    r.reward += full();
-    if (!o.done) lim = ladder_plain_limit<DIR>(m, e, pr);
-    rng.phase(3);
-    if (++r.ticks >= TICK_CAP) {
-      e.f |= E_TICKCAP;
-      break;
-    }
-  } while (!o.done);
+  } while (counted_tick(e, rng, r, TICK_DRAWS, [&]() { return full(lim); }) && !o.done);
 }
 
 // the while-not-done loop of _Option.run (OP/:28-31) for option K, whose can_run held
@@ -1619,96 +1637,50 @@ TG_HD void run_option_k(const Level& L, const uint32_t* trig, const Map& m, Env&
                         StepResult& r) {
   r.ran = 1;
   Opt o{0, false, false};
+  const auto policy_tick = [&]() {  // the option's policy and the primitive tick it chose
+    const int prim = policy<K>(L, m, e, o);
+    return tick<prims_of(K), R>(L, trig, m, e, prim, rng);
+  };
   if constexpr (K == O_GO_LEFT || K == O_GO_RIGHT) {
     constexpr int DIR = K == O_GO_LEFT ? -1 : 1;
-    int lim = DIR > 0 ? -0x40000000 : 0x40000000;  // no plain tick before the first full one
-    // Two phases per round.  Plain phase: every lane inside its span takes plain ticks until
-    // it leaves it (the loop body is just the plain tick).  Full phase: then no lane of the wave is in a span, and each takes one full
-    // tick, which may open a new span.  Each lane's own tick sequence is the reference's; only
-    // the interleaving across lanes differs, and the full tick's code runs once per round.
-    do {
-      // a lane leaves when its span ends; the wave when all have (a per-lane loop: a
-      // ballot-driven one, with the idle lanes kept inside, made the compiler copy ~26
-      // loop-carried registers per iteration and was slower)
-      // (the plain phase also ends when the staged draws run low: the full tick restocks them
-      // in rng.reserve, so the plain loop's body holds no refill code)
-      rng.phase(0);
-      if (const int t = rng.template walk<DIR>(e.px, lim, TICK_CAP - r.ticks)) {  // plain ticks
-        e.f = DIR > 0 ? (e.f | F_FACING) : (e.f & ~F_FACING);
-        r.reward -= t;
-        r.ticks += t;
-        if (DIR > 0 ? e.px > lim : e.px < lim) pickups(L, e);  // left the span: as the full tick
-        if (r.ticks >= TICK_CAP) {
-          e.f |= E_TICKCAP;
-          break;
-        }
-      }
-      rng.phase(1);
-      rng.reserve(TICK_DRAWS);
-      rng.phase(2);
-      const int prim = policy<K>(L, m, e, o);
-      r.reward += tick<prims_of(K), R>(L, trig, m, e, prim, rng);
+    span_loop<DIR, true>(L, e, e.px, o, rng, r, [&](int& lim) {
+      const int rew = policy_tick();
       if (!o.done) lim = go_plain_limit<DIR>(m, e, o.tx);
-      rng.phase(3);
-      if (++r.ticks >= TICK_CAP) {
-        e.f |= E_TICKCAP;
-        break;
-      }
-    } while (!o.done);
-    return;
-  }
-  if constexpr (K == O_UP_LADDER || K == O_DOWN_LADDER) {
+      return rew;
+    });
+  } else if constexpr (K == O_UP_LADDER || K == O_DOWN_LADDER) {
     constexpr int DIR = K == O_UP_LADDER ? -1 : 1;
     if (m.mk) {  // the level bitmasks: full ticks and span limits test bits, no cell probes
       const LadMasks lm(m, Map::dc_of(e.f), e.px);
-      ladder_loop<DIR>(L, m, e, o, rng, r, LadProbeMk{m, lm},
-                       [&]() { return ladder_tick<DIR>(L, m, lm, e, o, rng); });
-      return;
+      span_loop<DIR, false>(L, e, e.py, o, rng, r, [&](int& lim) {
+        const int rew = ladder_tick<DIR>(L, m, lm, e, o, rng);
+        if (!o.done) lim = ladder_plain_limit<DIR>(m, e, LadProbeMk{m, lm});
+        return rew;
+      });
+    } else {
+      span_loop<DIR, false>(L, e, e.py, o, rng, r, [&](int& lim) {
+        const int rew = policy_tick();
+        if (!o.done) lim = ladder_plain_limit<DIR>(m, e, LadProbe{m, e});
+        return rew;
+      });
     }
-    ladder_loop<DIR>(L, m, e, o, rng, r, LadProbe{m, e}, [&]() {
-      const int prim = policy<K>(L, m, e, o);
-      return tick<prims_of(K), R>(L, trig, m, e, prim, rng);
-    });
-    return;
-  }
-  if constexpr (K == O_JUMP_LEFT || K == O_JUMP_RIGHT || K == O_DOWN_LEFT || K == O_DOWN_RIGHT) {
+  } else if constexpr (K == O_JUMP_LEFT || K == O_JUMP_RIGHT || K == O_DOWN_LEFT ||
+                       K == O_DOWN_RIGHT) {
     AirCells ac{0u, 0u, 0u, 0u, -0x40000000, 0, 0u};  // holds nothing: built on the first air tick
-    {  // the first tick (the jump itself; the drop's target), outside the air ticks' loop
-      rng.phase(0);
-      rng.phase(1);
-      rng.reserve(TICK_DRAWS);
-      rng.phase(2);
-      const int prim = policy<K>(L, m, e, o);
-      r.reward += tick<prims_of(K), R>(L, trig, m, e, prim, rng);
-      rng.phase(3);
-      if (++r.ticks >= TICK_CAP) {
-        e.f |= E_TICKCAP;
-        return;
-      }
-    }
+    // the first tick (the jump itself; the drop's target), outside the air ticks' loop
+    rng.phase(0);
+    if (!counted_tick(e, rng, r, TICK_DRAWS, policy_tick)) return;
     while (!o.done) {
       rng.phase(0);
-      rng.phase(1);
-      rng.reserve(TICK_DRAWS);
-      rng.phase(2);
-      r.reward += air_tick<K>(L, trig, m, e, o, rng, ac);
-      rng.phase(3);
-      if (++r.ticks >= TICK_CAP) {
-        e.f |= E_TICKCAP;
+      if (!counted_tick(e, rng, r, TICK_DRAWS,
+                        [&]() { return air_tick<K>(L, trig, m, e, o, rng, ac); }))
         break;
-      }
     }
-    return;
+  } else {
+    const uint32_t draws = K == O_INTERACT ? L.interact_draws : TICK_DRAWS;
+    while (counted_tick(e, rng, r, draws, policy_tick) && !o.done) {  // a round is one full tick
+    }
   }
-  do {
-    rng.reserve(K == O_INTERACT ? L.interact_draws : TICK_DRAWS);
-    const int prim = policy<K>(L, m, e, o);
-    r.reward += tick<prims_of(K), R>(L, trig, m, e, prim, rng);
-    if (++r.ticks >= TICK_CAP) {
-      e.f |= E_TICKCAP;
-      break;
-    }
-  } while (!o.done);
 }
 template <class R>
 TG_HD void run_option(const Level& L, const uint32_t* trig, const Map& m, Env& e, int k,

@@ -23,6 +23,7 @@
 #include "tg_level.h"
 #include "tg_batch.h"
 #include "tg_twist.h"
+#include "tg_run_diag.h"  // (k_run's timing hooks: no-ops outside the diagnostic build)
 
 using namespace tg;
 
@@ -338,21 +339,10 @@ struct RngCodesT {
     nxc = read();  // code() reads one draw ahead
     return taken;
   }
-#ifdef TG_DIAG_STAMPS
-  // DIAGNOSTIC BUILD ONLY: s_memtime per phase of the option loops (tg_core.h run_option_k):
-  // ph[k] sums the time of the segments ending at stamp k (1 plain walk, 2 window refill,
-  // 3 full tick); rounds counts stamp 0
-  unsigned long long ph[4] = {0, 0, 0, 0}, last = 0;
-  uint32_t rounds = 0;
-  __device__ __forceinline__ void phase(int k) {
-    const unsigned long long now = __builtin_amdgcn_s_memtime();
-    if (last) ph[k] += now - last;
-    last = now;
-    rounds += k == 0;
-  }
-#else
-  __device__ __forceinline__ void phase(int) {}
-#endif
+  // the option loops' phase marks (tg_core.h counted_tick, span_loop): the diagnostic build's
+  // per-phase clock, nothing in the product (tg_run_diag.h)
+  RunPhaseClock clk;
+  __device__ __forceinline__ void phase(int k) { clk.mark(k); }
   // a draw was taken past the staged window (reserve's bound broken: flagged E_WINDOW)
   __device__ __forceinline__ bool overrun() const { return left > (uint32_t)WIN_DRAWS; }
   // one draw, consumed for its outcomes (draw_code); reserve() guarantees it is in the window

@@ -281,18 +281,6 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   kst_end(ks, kt0);
 }
 
-#ifdef TG_DIAG_STAMPS
-// DIAGNOSTIC BUILD ONLY (scripts/diag_stamps.py): per-wave s_memtime stamps of k_run
-constexpr int NSTAMP = 11;
-// per wave: 4 durations/counts, 100 MHz start and end, the option loop's phases (walk, refill,
-// full tick: lane 0's sums) and rounds
-constexpr int NSTAMP_WAVES = 1 << 17;
-__device__ unsigned long long g_stamps[NSTAMP_WAVES * NSTAMP];
-#define TG_STAMP(v) v = __builtin_amdgcn_s_memtime()
-#else
-#define TG_STAMP(v) (void)0
-#endif
-
 template <bool AUTORESET, bool FINAL>
 __global__ __launch_bounds__(RUN_BLOCK) void k_run(Soa S, int64_t n, Level L,
                                                 const uint32_t* __restrict__ grid, StepIO io,
@@ -368,19 +356,10 @@ __global__ __launch_bounds__(RUN_BLOCK) void k_run(Soa S, int64_t n, Level L,
   e.mti = 0u;
   int2 ep = make_int2(0, 0);
   uint32_t draws = 0;
-  int regens = 0;  // wave-uniform
   int lregen = 0;  // halves this lane regenerated in its option loop
   lds_u8* const wscr = (lds_u8*)win + (threadIdx.x >> 6) * WIN_WAVE_BYTES;
-  unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0;
-  TG_STAMP(t0);
-#ifdef TG_DIAG_STAMPS
-  const unsigned long long rt0 = __builtin_amdgcn_s_memrealtime();
-#endif
-  (void)t0; (void)t1; (void)t2; (void)t3;
-#ifdef TG_DIAG_STAMPS
-  unsigned long long ph1 = 0, ph2 = 0, ph3 = 0;
-  uint32_t prounds = 0;
-#endif
+  RunStamp stamp;  // the diagnostic build's per-wave timing (tg_run_diag.h): no code in the product
+  stamp.begin();
   if (live) {
     const int64_t at = (int64_t)seg * w.shard_cap + idx;
     i = w.lists[at];
@@ -388,14 +367,11 @@ __global__ __launch_bounds__(RUN_BLOCK) void k_run(Soa S, int64_t n, Level L,
     ep = w.wep[at];
     RngCodes rng(S.mt + i * MT_STORE, S.mc + i * MT_CODES, e.mti, wscr);
     rng.prime();  // issue the code loads now; the first draw comes after the policy setup
-    TG_STAMP(t1);
+    stamp.env_loaded();
     if (k != O_GO_LEFT && k != O_GO_RIGHT && k != O_INTERACT) __builtin_amdgcn_s_setprio(PRIO_SLOW);
     // k is wave-uniform: one specialised loop; L_RESET's envs run none (reward None)
     if (k != L_RESET) run_option(L, trig, m, e, k, rng, r);
-    TG_STAMP(t2);
-#ifdef TG_DIAG_STAMPS
-    ph1 = rng.ph[1], ph2 = rng.ph[2], ph3 = rng.ph[3], prounds = rng.rounds;
-#endif
+    stamp.option_done(rng.clk);
     r.done = is_done(e);
     rng.drain();  // before the first result store: no wait for the window stands behind them
     finish_step<AUTORESET, FINAL, false>(level_div(L), e, rng, i, r, ep, io);  // valid: k_classify's
@@ -414,49 +390,10 @@ __global__ __launch_bounds__(RUN_BLOCK) void k_run(Soa S, int64_t n, Level L,
   }
   __builtin_amdgcn_s_setprio(0);
   wave_stats(stats, 0, 0, r.ticks, (int)draws, AUTORESET ? (live && r.done) : 0,
-             regens + (__ballot(lregen != 0) ? wave_sum(lregen) : 0), true,
+             __ballot(lregen != 0) ? wave_sum(lregen) : 0, true,
              (int64_t)blockIdx.x / (BLOCK / RUN_BLOCK));
   kst_end(ks, kt0);
-#ifdef TG_DIAG_STAMPS
-  TG_STAMP(t3);
-  {
-    int mx = r.ticks;
-    for (int o = 32; o > 0; o >>= 1) mx = max(mx, __shfl_xor(mx, o, 64));
-    const int sum = wave_sum(r.ticks);
-    const unsigned long long bl = __ballot(live);
-    const int src = bl ? __ffsll((long long)bl) - 1 : 0;
-    const unsigned long long a1 = __shfl(t1, src, 64);
-    const unsigned long long a2 = __shfl(t2, src, 64);
-    const int wv = (blockIdx.x * RUN_BLOCK + threadIdx.x) >> 6;
-    const unsigned long long rt3 = __builtin_amdgcn_s_memrealtime();
-    // the phases of the lane whose option loop ran longest (the wave's own time)
-    int lmax = src;
-    unsigned long long best = 0;
-    for (int l = 0; l < 64; ++l) {
-      const unsigned long long tl = __shfl(ph1 + ph2 + ph3, l, 64);
-      if (((bl >> l) & 1ull) && tl > best) best = tl, lmax = l;
-    }
-    const unsigned long long p1 = __shfl(ph1, lmax, 64), p2 = __shfl(ph2, lmax, 64),
-                             p3 = __shfl(ph3, lmax, 64);
-    const uint32_t pr = __shfl(prounds, lmax, 64);
-    if ((threadIdx.x & 63) == 0 && wv < NSTAMP_WAVES) {
-      unsigned long long* const g = g_stamps + (size_t)wv * NSTAMP;
-      // an idle wave (no listed chunk) is option 15 with 1 iteration
-      g[0] = bl ? a1 - t0 : 0;
-      g[1] = bl ? a2 - a1 : 0;
-      g[2] = bl ? t3 - a2 : t3 - t0;
-      g[3] = bl ? (unsigned long long)mx | ((unsigned long long)sum << 32) | ((unsigned long long)k << 56)
-                : 1ull | (15ull << 56);
-      g[4] = rt0;
-      g[5] = rt3;
-      g[6] = p1;
-      g[7] = p2;
-      g[8] = p3;
-      g[9] = pr;
-      g[10] = (unsigned long long)regens;  // halves this wave regenerated from the queue
-    }
-  }
-#endif
+  stamp.wave_end(live, k, r.ticks, (int)((blockIdx.x * RUN_BLOCK + threadIdx.x) >> 6));
 }
 
 // ---- deferred regeneration of the listed stale MT halves (k_regen) ----------------------------

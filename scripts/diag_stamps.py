@@ -48,20 +48,12 @@ def main():
         ist = buf[idle, 4].astype(np.int64)
         ien = buf[idle, 5].astype(np.int64)
         t00 = buf[allw, 4].astype(np.int64).min()
-        ih = buf[idle, 10].astype(np.int64)
-        print("idle waves %d (refill queue only): halves %d (%.1f per wave, max %d); started by "
+        print("idle waves %d (no listed chunk): started by "
               "10%% %.1f 50%% %.1f 90%% %.1f us; ended by 10%% %.1f 50%% %.1f 90%% %.1f 100%% %.1f us"
-              % (idle.sum(), ih.sum(), ih.mean(), ih.max(),
+              % (idle.sum(),
                  *np.percentile((ist - t00) / 100.0, [10, 50, 90]),
                  *np.percentile((ien - t00) / 100.0, [10, 50, 90, 100])))
-        with_job = idle & (buf[:, 10] > 0)
-        if with_job.any():
-            jen = (buf[with_job, 5].astype(np.int64) - t00) / 100.0
-            print("idle waves that regenerated >= 1 half: %d, ended by 50%% %.1f 90%% %.1f 100%% %.1f us"
-                  % (with_job.sum(), *np.percentile(jen, [50, 90, 100])))
     act = allw & ~idle
-    oh = buf[act, 10].astype(np.int64)
-    print("option waves' queue halves: %d (%.2f per wave)" % (oh.sum(), oh.mean()))
     b = buf[act].astype(np.float64)
     mx = (buf[act, 3] & 0xFFFFFFFF).astype(np.float64)
     sm = ((buf[act, 3] >> 32) & 0xFFFFFF).astype(np.float64)
