@@ -90,28 +90,32 @@ __device__ __forceinline__ void stage_cells(uint32_t* lgrid, uint32_t* ltrig,
     for (int i = threadIdx.x; i < mk_words(L.W, L.H); i += NT) masks[i] = L.masks[i];
   __syncthreads();
 }
-__device__ __forceinline__ void stage_level(LdsLevel& lv, const uint32_t* __restrict__ grid,
-                                            const Level& L) {
+// what a kernel's lanes read of the staged level (win: the waves' areas, run_level_in_lds)
+struct LevelView {
+  const uint32_t* trig;
+  Map m;
+  uint8_t* win;
+};
+// the level staged in LDS of the calling kernel's own (includes the barrier)
+__device__ __forceinline__ LevelView level_in_lds(const uint32_t* __restrict__ grid, const Level& L) {
+  __shared__ LdsLevel lv;
   stage_cells(lv.grid, lv.trig, grid, L);
+  return {lv.trig, Map{reinterpret_cast<const uint8_t*>(lv.grid), L.W, L.H}, nullptr};
 }
-#define LEVEL_IN_LDS()                   \
-  __shared__ LdsLevel lv;                \
-  stage_level(lv, grid, L);              \
-  const uint32_t* const trig = lv.trig;  \
-  const Map m{reinterpret_cast<const uint8_t*>(lv.grid), L.W, L.H}
-// k_run's LDS: the waves' code windows (WIN_WAVE_BYTES each, at offset 0: 16-B aligned for the
-// LDS-DMA), then the level's grid words and bitmasks (Map::mk).  (Sized at launch for the
-// handle's level instead of the largest, with the rows' loads issued before the staging
-// barrier, it measured ~4 % slower for the masked policy: DESIGN.md §3.1.)
-#define RUN_LEVEL_IN_LDS()                                                                \
-  __shared__ uint4 run_lds[((RUN_BLOCK / 64) * WIN_WAVE_BYTES + MAX_CELLS + 4 * MK_MAX_WORDS) / 16]; \
-  __shared__ uint32_t ltrig[12];                                                          \
-  uint8_t* const win = reinterpret_cast<uint8_t*>(run_lds);                                \
-  uint32_t* const lgrid = reinterpret_cast<uint32_t*>(win + (RUN_BLOCK / 64) * WIN_WAVE_BYTES); \
-  uint32_t* const lmk = lgrid + grid_words(L.W, L.H);                                     \
-  stage_cells<RUN_BLOCK>(lgrid, ltrig, grid, L, lmk);                                     \
-  const uint32_t* const trig = ltrig;                                                     \
-  const Map m{reinterpret_cast<const uint8_t*>(lgrid), L.W, L.H, L.masks ? lmk : nullptr}
+// k_run's and k_flow's LDS: the NT / 64 waves' areas (WAVE_BYTES each, the code windows, at offset
+// 0: 16-B aligned for the LDS-DMA), then the level's grid words and bitmasks (Map::mk); includes
+// the barrier.  (Sized at launch for the handle's level instead of the largest, with the rows'
+// loads issued before the staging barrier, it measured ~4 % slower for the masked: DESIGN.md §3.1.)
+template <int NT, int WAVE_BYTES>
+__device__ __forceinline__ LevelView run_level_in_lds(const uint32_t* __restrict__ grid, const Level& L) {
+  __shared__ uint4 run_lds[((NT / 64) * WAVE_BYTES + MAX_CELLS + 4 * MK_MAX_WORDS) / 16];
+  __shared__ uint32_t ltrig[12];
+  uint8_t* const win = reinterpret_cast<uint8_t*>(run_lds);
+  uint32_t* const lgrid = reinterpret_cast<uint32_t*>(win + (NT / 64) * WAVE_BYTES);
+  uint32_t* const lmk = lgrid + grid_words(L.W, L.H);
+  stage_cells<NT>(lgrid, ltrig, grid, L, lmk);
+  return {ltrig, Map{reinterpret_cast<const uint8_t*>(lgrid), L.W, L.H, L.masks ? lmk : nullptr}, win};
+}
 
 __device__ __forceinline__ void store_obs(double* out, int64_t i, const double o[9]) {
   double* p = out + i * 9;
@@ -221,6 +225,71 @@ __device__ __noinline__ WordPair mt_pair_ool_sc1(const uint32_t* mt, uint32_t p)
   WordPair r;
   mt_pair(mt, p, r.w0, r.w1, Sc1Ld());
   return r;
+}
+// k_flow's env state, handed from wave to wave inside one launch (tg_flow.h "Coherence"): loads
+// past this CU's L1 (16 B at byte offset off of base: buffer_load_dwordx4 ... sc1), and
+// write-through (sc1) stores, which leave the CU for the XCD's L2 before the storing wave's
+// `s_waitcnt vmcnt(0)` lets it publish them (plain stores were seen stale by the consumer: the
+// bring-up runs read unwritten list entries)
+__device__ __forceinline__ uint4 ld16_sc1(const void* base, uint32_t off) {
+  const __amdgpu_buffer_rsrc_t r =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, -1, 0x00020000);
+  const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 16 /* sc1 */);
+  return make_uint4(v[0], v[1], v[2], v[3]);
+}
+__device__ __forceinline__ double2 ld_ang_sc1(const double2* a, int64_t i) {
+  const uint4 v = ld16_sc1(a, (uint32_t)i * 16u);
+  return make_double2(__hiloint2double((int)v.y, (int)v.x), __hiloint2double((int)v.w, (int)v.z));
+}
+__device__ __forceinline__ int2 ld_ep_sc1(const int2* p, int64_t i) {
+  const uint64_t v = __hip_atomic_load(reinterpret_cast<const uint64_t*>(p + i), __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
+  return make_int2((int)(uint32_t)v, (int)(uint32_t)(v >> 32));
+}
+__device__ __forceinline__ void st16_sc1(void* base, uint32_t off, uint4 v) {
+  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(base, (short)0, -1, 0x00020000);
+  typedef unsigned v4u __attribute__((ext_vector_type(4)));
+  const v4u w = {v.x, v.y, v.z, v.w};
+  __builtin_amdgcn_raw_buffer_store_b128(w, r, off, 0, 16 /* sc1 */);
+}
+__device__ __forceinline__ void st_ep_sc1(int2* p, int64_t i, int2 v) {
+  __hip_atomic_store(reinterpret_cast<uint64_t*>(p + i),
+                     (uint64_t)(uint32_t)v.x | ((uint64_t)(uint32_t)v.y << 32), __ATOMIC_RELAXED,
+                     __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ uint4 d2u4(double2 d) {
+  const uint64_t a = (uint64_t)__double_as_longlong(d.x), b = (uint64_t)__double_as_longlong(d.y);
+  return make_uint4((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32));
+}
+// one env's state words: from the arrays st4 / ang / ep at index at (the handle's, or k_run's
+// worklist-ordered copies), and back to the handle's (ep_too false: the episode words are
+// unchanged, a reward-None step: no store).  FLOW: k_flow's forms above
+template <bool FLOW>
+__device__ __forceinline__ void load_env(const uint4* st4, const double2* ang, const int2* ep, int64_t at,
+                                         uint4& s4, double2& a2, int2& e2) {
+  s4 = FLOW ? ld16_sc1(st4, (uint32_t)at * 16u) : st4[at];
+  a2 = FLOW ? ld_ang_sc1(ang, at) : ang[at];
+  e2 = FLOW ? ld_ep_sc1(ep, at) : ep[at];
+}
+template <bool FLOW>
+__device__ __forceinline__ void load_env(const uint4* st4, const double2* ang, const int2* ep, int64_t at,
+                                         Env& e, int2& e2) {
+  uint4 s4;
+  double2 a2;
+  load_env<FLOW>(st4, ang, ep, at, s4, a2, e2);
+  unpack(s4, a2, e);
+}
+template <bool FLOW>
+__device__ __forceinline__ void store_env(const Soa& S, int64_t i, const Env& e, int2 ep, bool ep_too = true) {
+  if constexpr (FLOW) {
+    st16_sc1(S.st4, (uint32_t)i * 16u, pack(e));
+    st16_sc1(S.ang, (uint32_t)i * 16u, d2u4(make_double2(e.ang0, e.ang1)));
+    st_ep_sc1(S.ep, i, ep);
+  } else {
+    S.st4[i] = pack(e);
+    S.ang[i] = make_double2(e.ang0, e.ang1);
+    if (ep_too) S.ep[i] = ep;
+  }
 }
 
 template <bool FLOW = false>  // FLOW: k_flow's L1-bypassing loads (tg_flow.h)
@@ -632,6 +701,40 @@ __device__ __forceinline__ void store_obs_wave(double* __restrict__ out, int64_t
   }
 }
 
+// ---- one env's step after its option (step_env; k_run's and k_flow's run_listed) ---------------
+// The env's rows, its MT state word (a half left here: MT_STALE, listed by the next
+// classification), the lane's draws and own regenerations, its error bits.  The per-step kernels
+// land the window before their first result store; k_flow keeps the wait in RngCodesT::finish
+template <bool AUTORESET, bool FINAL, bool VALID, bool FLOW>
+__device__ __forceinline__ void finish_env(const Level& L, Env& e, RngCodesT<FLOW>& rng, int64_t i,
+                                           const StepResult& r, int2& ep, const StepIO& io,
+                                           uint32_t* err_or, uint32_t& draws, int& lregen) {
+  if constexpr (!FLOW) rng.drain();
+  finish_step<AUTORESET, FINAL, VALID>(level_div(L), e, rng, i, r, ep, io);
+  e.mti = rng.finish();
+  draws = rng.draws;
+  lregen = (int)rng.regens;
+  if (e.f & E_MASK) atomicOr(err_or, e.f & E_MASK);
+}
+// The wave's epilogue: completed episodes, the envs' state back, the launch counters (slot sl).
+// ep_in: the episode words as loaded (stored only if changed), or null (always stored).  steps /
+// valid / wregens: counted where the caller steps whole envs.  Every lane of the wave reaches it.
+template <bool AUTORESET, bool FLOW, bool ONE = false>  // ONE: only lane 0 live (k_serve1)
+__device__ __forceinline__ void run_epilogue(const Soa& S, bool live, int64_t i, int64_t g, const Env& e,
+                                             int2& ep, const int2* ep_in, const StepResult& r,
+                                             uint32_t draws, int lregen, uint32_t tstep, const EpQueue& q,
+                                             unsigned long long* __restrict__ stats, int64_t sl, int steps = 0,
+                                             int valid = 0, int wregens = 0) {
+  if (AUTORESET) record_episodes(live && r.done, g, ep, tstep, q, stats, sl);
+  if (live) store_env<FLOW>(S, i, e, ep, !ep_in || ep.x != ep_in->x || ep.y != ep_in->y);
+  __builtin_amdgcn_s_setprio(0);
+  const int eps = AUTORESET ? (live && r.done) : 0;
+  if constexpr (ONE)
+    lane0_stats(stats, steps, valid, r.ticks, (int)draws, eps, wregens + lregen, true);
+  else
+    wave_stats(stats, steps, valid, r.ticks, (int)draws, eps,
+               wregens + (__ballot(lregen != 0) ? wave_sum(lregen) : 0), true, sl);
+}
 // ---- one-pass step: one lane per env, the option runs in place (TG_MODE_DIRECT) ----------
 constexpr int POL_IMMEDIATE = -2;  // k_step's action is io.a0 (tg_step1), not an array entry
 // POL: -1 actions given; POL_IMMEDIATE one action for all (tg_step1); else the TG_POLICY_*
@@ -654,8 +757,7 @@ __device__ __forceinline__ StepResult step_env(const Soa& S, int64_t n, const Le
   e.mti = 0u;
   int2 ep = make_int2(0, 0), ep_in = ep;
   if (live) {
-    unpack(S.st4[i], S.ang[i], e);
-    ep = S.ep[i];
+    load_env<false>(S.st4, S.ang, S.ep, i, e, ep);
     ep_in = ep;
     RngCodes rng(S.mt + i * MT_STORE, S.mc + i * MT_CODES, e.mti, wscr);
     int act;
@@ -668,31 +770,15 @@ __device__ __forceinline__ StepResult step_env(const Soa& S, int64_t n, const Le
       act = io.actions[i];
     }
     r = env_step(L, trig, m, e, act, rng);
-    rng.drain();  // before the first result store (RngCodes::finish)
-    finish_step<AUTORESET, FINAL>(level_div(L), e, rng, i, r, ep, io);
-    e.mti = rng.finish();
-    draws = rng.draws;
-    lregen = (int)rng.regens;
-    if (e.f & E_MASK) atomicOr(err_or, e.f & E_MASK);
+    finish_env<AUTORESET, FINAL, true>(L, e, rng, i, r, ep, io, err_or, draws, lregen);
   }
   // one pass, no classify pass after it: regenerate the halves left in this launch now
   const unsigned long long need = __ballot(live && (e.mti & MT_STALE));
-  wave_refill(need, S.mt + (live ? i : 0) * MT_STORE,
-              S.mc + (live ? i : 0) * MT_CODES, e.mti,
+  wave_refill(need, S.mt + (live ? i : 0) * MT_STORE, S.mc + (live ? i : 0) * MT_CODES, e.mti,
               (lds_u32*)wscr);
   e.mti &= ~(MT_STALE | MT_LISTED);
-  if (AUTORESET) record_episodes(live && r.done, g0 + i, ep, io.tstep, q, stats, blockIdx.x);
-  if (live) {
-    S.st4[i] = pack(e);
-    S.ang[i] = make_double2(e.ang0, e.ang1);
-    if (ep.x != ep_in.x || ep.y != ep_in.y) S.ep[i] = ep;  // a reward-None step changes nothing
-  }
-  if constexpr (ONE)
-    lane0_stats(stats, live ? 1 : 0, r.ran, r.ticks, (int)draws, AUTORESET ? (live && r.done) : 0,
-                __popcll(need) + lregen, true);
-  else
-    wave_stats(stats, live ? 1 : 0, r.ran, r.ticks, (int)draws, AUTORESET ? (live && r.done) : 0,
-               __popcll(need) + wave_sum(lregen), true);
+  run_epilogue<AUTORESET, false, ONE>(S, live, i, g0 + i, e, ep, &ep_in, r, draws, lregen, io.tstep, q,
+                                      stats, blockIdx.x, live ? 1 : 0, r.ran, __popcll(need));
   return r;
 }
 
@@ -711,18 +797,19 @@ constexpr int WSHARDS = TG_WSHARDS;
 // pair's f64 library code held it at 79 VGPRs, 6 waves per SIMD; without it 58, 8 waves)
 constexpr int L_RESET = O_COUNT;
 constexpr int NLIST = O_COUNT + 1;
-constexpr int kOrderH[NLIST] = {O_JUMP_LEFT, O_JUMP_RIGHT, O_GO_LEFT,     O_GO_RIGHT,
-                                O_DOWN_LEFT, O_DOWN_RIGHT, O_UP_LADDER,   O_DOWN_LADDER,
-                                O_INTERACT,  L_RESET};
-struct RunPos {
-  int of[NLIST];  // run position of list k (kOrder's inverse)
+// the run order of the lists (k_run, tg_kernels.h: why this order), and its inverse
+struct RunOrder {
+  int list[NLIST];      // the list run at position j
+  int seg_base[NLIST];  // list k's first segment: its run position * WSHARDS
 };
-constexpr RunPos make_runpos() {
-  RunPos r{};
-  for (int j = 0; j < NLIST; ++j) r.of[kOrderH[j]] = j;
+constexpr RunOrder make_run_order() {
+  RunOrder r{{O_JUMP_LEFT, O_JUMP_RIGHT, O_GO_LEFT, O_GO_RIGHT, O_DOWN_LEFT, O_DOWN_RIGHT,
+              O_UP_LADDER, O_DOWN_LADDER, O_INTERACT, L_RESET},
+             {}};
+  for (int j = 0; j < NLIST; ++j) r.seg_base[r.list[j]] = j * WSHARDS;
   return r;
 }
-constexpr RunPos kRunPos = make_runpos();
+constexpr RunOrder kRunOrder = make_run_order();
 constexpr int NSEG = NLIST * WSHARDS;  // segment = run position * WSHARDS + shard
 static_assert(NSEG <= 2 * RUN_BLOCK, "k_run's prefix: two segments per thread");
 constexpr int NCTR = NSEG;      // the worklist counters
@@ -749,6 +836,93 @@ constexpr int REGEN_STEPS = 16;
 // regen_ctr, per set: the 8 grab counters, then the 8 list lengths (k_classify's rcnt)
 constexpr int RCTR_LIST = 8;
 constexpr int RCTR_N = 16;
+
+// ---- one env's step in two halves: decide (k_classify, k_flow's classification) and run (k_run,
+// k_flow's run items) ------------------------------------------------------------------------------
+struct EnvClass {
+  bool runs, rst;  // the option can run; it cannot, and the env enters done with auto-reset on
+  bool stale;      // its stale MT half goes on the refill list now
+  int bk;          // the env's worklist (rst: L_RESET), -1: none (its step is none_rows')
+};
+// POL >= 0: the rollout's on-device policy (tg_rollout), its action written to io.actions (if
+// given); else act_in.  Sets E_ACTION; marks a half left stale and not listed yet MT_LISTED:
+// k_regen regenerates the lists of several steps at once (a lane that needs a half first does it
+// itself: the ring leaves >= ~2,400 draws of slack, launch_step)
+template <bool AUTORESET, int POL>
+__device__ __forceinline__ EnvClass classify_env(const Level& L, const Map& m, Env& e, bool live,
+                                                 int act, const StepIO& io, int64_t i, int64_t g) {
+  EnvClass c{false, false, false, -1};
+  int k = -1;
+  if (live) {
+    if constexpr (POL >= 0) {
+      act = policy_action(L, m, e, POL, io.a0, g, io.t);
+      if (io.actions) io.actions[i] = act;
+    }
+    k = option_index(act);
+    c.runs = k >= 0 && can_run(L, m, e, k);
+    if (k < 0) e.f |= E_ACTION;
+  }
+  c.rst = AUTORESET && live && !c.runs && is_done(e);
+  c.bk = c.runs ? k : c.rst ? L_RESET : -1;
+  c.stale = live && (e.mti & (MT_STALE | MT_LISTED)) == MT_STALE;
+  if (c.stale) e.mti |= MT_LISTED;
+  return c;
+}
+// a refill list's entry: env | source half
+__device__ __forceinline__ uint32_t refill_entry(int64_t i, uint32_t mti) {
+  return (uint32_t)i | (mt_half(mti & MT_POS_MASK) ? 0x80000000u : 0u);
+}
+// the step of the wave's envs whose option cannot run (fin; not L_RESET's): reward None, state
+// unchanged (TG/:91-96, OP/:22-23), the obs rows through the wave's LDS `stage`.  The valid row
+// is the caller's.  Every lane of the wave reaches it.
+template <bool FINAL>
+__device__ __forceinline__ void none_rows(const Level& L, const Soa& S, bool fin, Env& e, double2 a2,
+                                          int64_t i, int2& ep, const StepIO& io, double* stage,
+                                          uint32_t* err_or) {
+  double orow[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  if (fin) {
+    e.ang0 = a2.x;
+    e.ang1 = a2.y;
+    Rng rng(S.mt + i * MT_STORE, e.mti, S.mc + i * MT_CODES);  // no draws without a reset
+    StepResult r{0, 0, (int)is_done(e), 0};
+    finish_step<false, FINAL, false>(L, e, rng, i, r, ep, io, orow);
+    if (e.f & E_MASK) atomicOr(err_or, e.f & E_MASK);
+  }
+  store_obs_wave(io.obs, i - (threadIdx.x & 63), __ballot(fin), orow, stage);
+}
+// the wave's lanes grouped by list (bk >= 0): the lane's rank in its group, the group's first
+// lane and its size.  Must be reached by every lane of the wave.
+struct LaneGroup {
+  int rank, lead, nb;
+};
+__device__ __forceinline__ LaneGroup lane_groups(int bk) {
+  LaneGroup g{0, 0, 0};
+  unsigned long long pend = __ballot(bk >= 0);
+  while (pend) {
+    const int first = __ffsll((long long)pend) - 1;
+    const int b0 = __builtin_amdgcn_readlane(bk, first);
+    const unsigned long long b = __ballot(bk == b0);
+    if (bk == b0) g = {(int)__popcll(b & ((1ull << (threadIdx.x & 63)) - 1ull)), first, (int)__popcll(b)};
+    pend &= ~b;
+  }
+  return g;
+}
+// A listed env's step from its loaded state through its rows (valid: the deciding pass's): option
+// k, wave-uniform (one specialised loop; L_RESET: none, reward None).  hook: RunStamp or NoRunHook
+template <bool AUTORESET, bool FINAL, bool FLOW, class Hook>
+__device__ __forceinline__ void run_listed(const Level& L, const uint32_t* trig, const Map& m, const Soa& S,
+                                           int64_t i, int k, Env& e, int2& ep, lds_u8* wscr,
+                                           const StepIO& io, uint32_t* err_or, StepResult& r,
+                                           uint32_t& draws, int& lregen, Hook& hook) {
+  RngCodesT<FLOW> rng(S.mt + i * MT_STORE, S.mc + i * MT_CODES, e.mti, wscr);
+  rng.prime();  // issue the code loads now; the first draw comes after the policy setup
+  hook.env_loaded();
+  if (k != O_GO_LEFT && k != O_GO_RIGHT && k != O_INTERACT) __builtin_amdgcn_s_setprio(PRIO_SLOW);
+  if (k != L_RESET) run_option(L, trig, m, e, k, rng, r);
+  hook.option_done(rng.clk);
+  r.done = is_done(e);
+  finish_env<AUTORESET, FINAL, false>(L, e, rng, i, r, ep, io, err_or, draws, lregen);
+}
 }  // namespace
 
 // k_flow<AR, POL> is instantiated in its own translation unit, tg_flow.hip, which is built

@@ -1,8 +1,9 @@
 // tg_flow.h — k_flow: tg_rollout's K steps in ONE launch, each 64-env chunk advancing to its
 // next step as soon as its own envs have finished the current one (TG_MODE_FLOW, §8f row 3).
-// Built on tg_dev.h's pieces of the per-step kernels (RngCodesT, finish_step, store_obs_wave,
-// record_episodes, wave_stats).  tg_flow.hip instantiates k_flow; tg_amd.hip includes this header
-// for the Flow / FlowIO types and constants its host code fills in (launch_flow).
+// One env's step is tg_dev.h's, shared with the per-step kernels (classify_env, none_rows,
+// lane_groups; run_listed, run_epilogue; load_env / store_env past the L1); written here is the
+// protocol: work loop, reservations, publishing waits.  tg_flow.hip instantiates k_flow; tg_amd.hip
+// includes this header for the Flow / FlowIO types and constants its host code fills (launch_flow).
 //
 // Why: the reference's step is per env (TG/:91-96 -> OP/:20-36): env i's step
 // t + 1 depends on env i's step t only.  The per-step kernels put a batch-wide barrier after
@@ -110,51 +111,14 @@ struct FlowIO {
 };
 
 __device__ __forceinline__ int32_t* fcw(int32_t* ctl, int w) { return ctl + w * FC_STRIDE; }
-__device__ __forceinline__ int32_t ld_sc1(const int32_t* p) {
+template <class T>  // (int32_t, uint32_t)
+__device__ __forceinline__ T ld_sc1(const T* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ uint32_t ld_sc1(const uint32_t* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// 16 B at byte offset off of base, past this CU's L1 (buffer_load_dwordx4 ... sc1)
-__device__ __forceinline__ uint4 ld16_sc1(const void* base, uint32_t off) {
-  const __amdgpu_buffer_rsrc_t r =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, -1, 0x00020000);
-  const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 16 /* sc1 */);
-  return make_uint4(v[0], v[1], v[2], v[3]);
-}
-// write-through (sc1) stores of handed-off bytes: they leave the CU for the XCD's L2 before the
-// storing wave's `s_waitcnt vmcnt(0)` lets it publish them (plain stores were seen stale by the
-// consumer: the bring-up runs read unwritten list entries)
-__device__ __forceinline__ void st_sc1(int32_t* p, int32_t v) {
+// write-through (sc1) stores of handed-off words, as the env state's (tg_dev.h store_env)
+template <class T>
+__device__ __forceinline__ void st_sc1(T* p, T v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st_sc1(uint32_t* p, uint32_t v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st16_sc1(void* base, uint32_t off, uint4 v) {
-  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(base, (short)0, -1, 0x00020000);
-  typedef unsigned v4u __attribute__((ext_vector_type(4)));
-  const v4u w = {v.x, v.y, v.z, v.w};
-  __builtin_amdgcn_raw_buffer_store_b128(w, r, off, 0, 16 /* sc1 */);
-}
-__device__ __forceinline__ void st_ep_sc1(int2* p, int64_t i, int2 v) {
-  __hip_atomic_store(reinterpret_cast<uint64_t*>(p + i),
-                     (uint64_t)(uint32_t)v.x | ((uint64_t)(uint32_t)v.y << 32), __ATOMIC_RELAXED,
-                     __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint4 d2u4(double2 d) {
-  const uint64_t a = (uint64_t)__double_as_longlong(d.x), b = (uint64_t)__double_as_longlong(d.y);
-  return make_uint4((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32));
-}
-__device__ __forceinline__ double2 ld_ang_sc1(const double2* a, int64_t i) {
-  const uint4 v = ld16_sc1(a, (uint32_t)i * 16u);
-  return make_double2(__hiloint2double((int)v.y, (int)v.x), __hiloint2double((int)v.w, (int)v.z));
-}
-__device__ __forceinline__ int2 ld_ep_sc1(const int2* p, int64_t i) {
-  const uint64_t v = __hip_atomic_load(reinterpret_cast<const uint64_t*>(p + i), __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);
-  return make_int2((int)(uint32_t)v, (int)(uint32_t)(v >> 32));
 }
 // the 100 MHz constant clock, read where it stands (volatile: never hoisted out of a spin)
 __device__ __forceinline__ unsigned long long realtime() {
@@ -208,17 +172,10 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4))) void
     const int64_t nf = (int64_t)f.P * FLOW_MAX_K * NLIST * f.jcap;
     for (int64_t w = gt; w < nf; w += gs) f.fill_next[w] = 0;
   }
-  __shared__ uint4 flds[((BLOCK / 64) * FLOW_WAVE_BYTES + MAX_CELLS + 4 * MK_MAX_WORDS) / 16];
-  __shared__ uint32_t ltrig[12];
-  uint8_t* const wall = reinterpret_cast<uint8_t*>(flds);
-  uint32_t* const lgrid = reinterpret_cast<uint32_t*>(wall + (BLOCK / 64) * FLOW_WAVE_BYTES);
-  uint32_t* const lmk = lgrid + grid_words(L.W, L.H);
-  stage_cells<BLOCK>(lgrid, ltrig, grid, L, lmk);  // the only barrier
-  const uint32_t* const trig = ltrig;
-  const Map m{reinterpret_cast<const uint8_t*>(lgrid), L.W, L.H, L.masks ? lmk : nullptr};
+  const LevelView lv = run_level_in_lds<BLOCK, FLOW_WAVE_BYTES>(grid, L);  // the only barrier
 
   const int lane = threadIdx.x & 63;
-  uint8_t* const warea = wall + (threadIdx.x >> 6) * FLOW_WAVE_BYTES;
+  uint8_t* const warea = lv.win + (threadIdx.x >> 6) * FLOW_WAVE_BYTES;
   const int x = (int)((f.xmap >> (4u * (xcc_id() & 7u))) & 0xFu);
   FLOW_DBG(1, x, 0, 0);
   if (x >= f.P || x == f.skip) {  // an XCD the census did not see: no sub-problem (the workgroup)
@@ -249,9 +206,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4))) void
     else atomicOr(err_or, E_FLOW);  // (capacity is the bound of the pushes: unreachable)
   };
   auto step_io = [&](int t) {
-    return StepIO{nullptr, io.obs + (int64_t)t * io.obs_stride, io.reward + (int64_t)t * n,
-                  io.valid + (int64_t)t * n, io.done + (int64_t)t * n, nullptr, POL, io.a0,
-                  io.t0 + t, io.tb + (uint32_t)t};
+    return StepIO{io.actions ? io.actions + (int64_t)t * n : nullptr,
+                  io.obs + (int64_t)t * io.obs_stride, io.reward + (int64_t)t * n, io.valid + (int64_t)t * n,
+                  io.done + (int64_t)t * n, nullptr, POL, io.a0, io.t0 + t, io.tb + (uint32_t)t};
   };
 
   // classify chunk c for step t (k_classify's per-env work); returns the envs it listed
@@ -262,74 +219,35 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4))) void
     uint4 s4 = make_uint4(0, 0, 0, 0);
     double2 a2 = make_double2(0.0, 0.0);
     int2 ep = make_int2(0, 0);
-    if (live) {
-      s4 = ld16_sc1(S.st4, (uint32_t)i * 16u);
-      a2 = ld_ang_sc1(S.ang, i);
-      ep = ld_ep_sc1(S.ep, i);
-    }
     Env e;
     e.mti = 0u;
-    int k = -1;
-    bool runs = false;
     if (live) {
+      load_env<true>(S.st4, S.ang, S.ep, i, s4, a2, ep);
       unpack_st4(s4, e);
       FLOW_EV_WAVE(11, c, t);  // (timing log: the state loads returned)
-      const int act = policy_action(L, m, e, POL, io.a0, g0 + i, io.t0 + t);
-      if (io.actions) io.actions[(int64_t)t * n + i] = act;
-      k = option_index(act);
-      runs = k >= 0 && can_run(L, m, e, k);
-      if (k < 0) e.f |= E_ACTION;
     }
-    const bool rst = AR && live && !runs && is_done(e);  // entering done: reset (L_RESET)
-    const int bk = runs ? k : rst ? L_RESET : -1;
+    const auto [runs, rst, stale, bk] = classify_env<AR, POL>(L, lv.m, e, live, 0, st, i, g0 + i);
     // The atomics that reserve this chunk's places go out first, their round trips overlapping
     // the rows below (each one on the chain cost a classification ~1 us, the r05h event log):
     // stale MT halves not listed yet go on k_regen's list c % SHARDS ...
-    const bool stale = live && (e.mti & (MT_STALE | MT_LISTED)) == MT_STALE;
     const unsigned long long sb = __ballot(stale);
     int sbase = 0;
     if (sb && lane == 0) sbase = atomicAdd(&f.rcnt[(c % SHARDS) * CTR_STRIDE], __popcll(sb));
-    if (stale) e.mti |= MT_LISTED;
-    // ... and the listed lanes, grouped by list (rank in the group, its first lane and size),
-    // reserve their entries
-    const unsigned long long lb = __ballot(bk >= 0);
-    const int cnt = __popcll(lb);
-    int rank = 0, lead = 0, nb = 0;
-    unsigned long long pend = lb;
-    while (pend) {
-      const int first = __ffsll((long long)pend) - 1;
-      const int b0 = __builtin_amdgcn_readlane(bk, first);
-      const unsigned long long b = __ballot(bk == b0);
-      if (bk == b0) {
-        rank = __popcll(b & lt_mask);
-        lead = first;
-        nb = __popcll(b);
-      }
-      pend &= ~b;
-    }
+    // ... and the listed lanes, grouped by list, reserve their entries
+    const int cnt = __popcll(__ballot(bk >= 0));
+    const auto [rank, lead, nb] = lane_groups(bk);
     const int lidx = t * NLIST + (bk >= 0 ? bk : 0);
     int base = 0;
     if (bk >= 0 && lane == lead) base = atomicAdd(fcw(ctl, FC_LTAIL + lidx), nb);
     // every env's valid row, coalesced (as k_classify); the rows of the envs whose option cannot
     // run: reward None, state unchanged (TG/:91-96, OP/:22-23)
     if (live) st.valid[i] = (uint8_t)runs;
-    const bool fin = live && !runs && !rst;
-    double orow[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (fin) {
-      e.ang0 = a2.x;
-      e.ang1 = a2.y;
-      Rng rng(S.mt + i * MT_STORE, e.mti, S.mc + i * MT_CODES);  // no draws without a reset
-      StepResult r{0, 0, (int)is_done(e), 0};
-      finish_step<false, false, false>(L, e, rng, i, r, ep, st, orow);
-    }
-    if (fin && (e.f & E_MASK)) atomicOr(err_or, e.f & E_MASK);
-    store_obs_wave(st.obs, (int64_t)c * 64, __ballot(fin), orow, reinterpret_cast<double*>(warea));
+    none_rows<false>(L, S, live && !runs && !rst, e, a2, i, ep, st, (double*)warea, err_or);
     FLOW_EV_WAVE(12, c, t);  // (timing log: the rows issued)
     // the handed-off bytes: refill entries, list entries, the state, the chunk's count
     sbase = __builtin_amdgcn_readlane(sbase, 0);
     if (stale)
-      f.refill[(c % SHARDS) * f.rcap + sbase + __popcll(sb & lt_mask)] =
-          (uint32_t)i | (mt_half(e.mti & MT_POS_MASK) ? 0x80000000u : 0u);
+      f.refill[(c % SHARDS) * f.rcap + sbase + __popcll(sb & lt_mask)] = refill_entry(i, e.mti);
     base = __shfl(base, lead, 64);
     if (bk >= 0) st_sc1(list + (int64_t)lidx * f.lcap + base + rank, (int32_t)i);
     if (live) {
@@ -367,62 +285,47 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4))) void
   // one run item: the option loops of a 64-entry list chunk (k_run's per-env work); returns the
   // lanes whose env's chunk became ready (its chunk in cl)
   auto run = [&](uint32_t item, int& cl) -> unsigned long long {
-      const int t = (int)(item >> 28), k = (int)((item >> 24) & 15u), j = (int)(item & 0xFFFFFFu);
-      // a cheap guard: an item or entry out of range is a protocol bug; it sets
-      // TG_ERR_FLOW and runs nothing instead of addressing memory with it
-      const bool item_ok = t < K && k < NLIST && (int64_t)j < f.jcap;
-      const int lidx = item_ok ? t * NLIST + k : 0;
-      int tail = 0;
-      if (lane == 0 && item_ok) tail = ld_sc1(fcw(ctl, FC_LTAIL + lidx));
-      tail = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_readlane(tail, 0));
-      const int mcnt = item_ok ? min(64, tail - 64 * j) : 0;
-      bool live = lane < mcnt;
-      int64_t i = 0;
-      if (live) i = ld_sc1(list + (int64_t)lidx * f.lcap + 64 * j + lane);
-      const bool bad = live && (i < 0 || i >= n || (int)((i >> 6) % P) != x);
-      if (lane == 0 && (!item_ok || __ballot(bad))) atomicOr(err_or, E_FLOW);
-      live = live && !bad;
-      FLOW_DIAG_RUN(item, i, live, mcnt, tail, lidx, j);
-      const StepIO st = step_io(t);
-      StepResult r{0, 0, 0, 0};
-      Env e;
-      e.mti = 0u;
-      int2 ep = make_int2(0, 0);
-      uint32_t draws = 0;
-      int lregen = 0;
-      if (live) {
-        unpack(ld16_sc1(S.st4, (uint32_t)i * 16u), ld_ang_sc1(S.ang, i), e);
-        ep = ld_ep_sc1(S.ep, i);
-        RngCodesT<true> rng(S.mt + i * MT_STORE, S.mc + i * MT_CODES, e.mti, (lds_u8*)warea);
-        rng.prime();
-        if (k != O_GO_LEFT && k != O_GO_RIGHT && k != O_INTERACT) __builtin_amdgcn_s_setprio(PRIO_SLOW);
-          if (k != L_RESET) run_option(L, trig, m, e, k, rng, r);  // k is wave-uniform
-        r.done = is_done(e);
-        finish_step<AR, false, false>(level_div(L), e, rng, i, r, ep, st);
-        e.mti = rng.finish();
-        draws = rng.draws;
-        lregen = (int)rng.regens;
-        if (e.f & E_MASK) atomicOr(err_or, e.f & E_MASK);
-      }
-      if (AR) record_episodes(live && r.done, g0 + i, ep, st.tstep, eq, stats, slot);
-      if (live) {
-        st16_sc1(S.st4, (uint32_t)i * 16u, pack(e));
-        st16_sc1(S.ang, (uint32_t)i * 16u, d2u4(make_double2(e.ang0, e.ang1)));
-        st_ep_sc1(S.ep, i, ep);
-      }
-      __builtin_amdgcn_s_setprio(0);
-      wave_stats(stats, 0, 0, r.ticks, (int)draws, AR ? (live && r.done) : 0,
-                 __ballot(lregen != 0) ? wave_sum(lregen) : 0, true, slot);
-      // this wave's stores first, then the chunks' counters: the lane that takes its env's chunk
-      // to 0 hands the chunk to the wave (classified for t + 1 below, in lane order)
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      int old = 0;
-      if (live) old = atomicSub(&f.outst[i >> 6], 1);
-      if (live) FLOW_EV_LANE(3, item, (uint32_t)i, (uint32_t)old, (uint32_t)lane | ((uint32_t)mcnt << 8) | ((uint32_t)x << 16));
-      unsigned long long ready = __ballot(live && old == 1);
-      if (lane == 0) FLOW_EV(7, item, (uint32_t)__popcll(ready), (uint32_t)mcnt, x);
-      cl = (int)(i >> 6);
-      return ready;
+    const int t = (int)(item >> 28), k = (int)((item >> 24) & 15u), j = (int)(item & 0xFFFFFFu);
+    // a cheap guard: an item or entry out of range is a protocol bug; it sets
+    // TG_ERR_FLOW and runs nothing instead of addressing memory with it
+    const bool item_ok = t < K && k < NLIST && (int64_t)j < f.jcap;
+    const int lidx = item_ok ? t * NLIST + k : 0;
+    int tail = 0;
+    if (lane == 0 && item_ok) tail = ld_sc1(fcw(ctl, FC_LTAIL + lidx));
+    tail = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_readlane(tail, 0));
+    const int mcnt = item_ok ? min(64, tail - 64 * j) : 0;
+    bool live = lane < mcnt;
+    int64_t i = 0;
+    if (live) i = ld_sc1(list + (int64_t)lidx * f.lcap + 64 * j + lane);
+    const bool bad = live && (i < 0 || i >= n || (int)((i >> 6) % P) != x);
+    if (lane == 0 && (!item_ok || __ballot(bad))) atomicOr(err_or, E_FLOW);
+    live = live && !bad;
+    FLOW_DIAG_RUN(item, i, live, mcnt, tail, lidx, j);
+    const StepIO st = step_io(t);
+    StepResult r{0, 0, 0, 0};
+    Env e;
+    e.mti = 0u;
+    int2 ep = make_int2(0, 0);
+    uint32_t draws = 0;
+    int lregen = 0;
+    if (live) {
+      load_env<true>(S.st4, S.ang, S.ep, i, e, ep);
+      NoRunHook hook;
+      run_listed<AR, false, true>(L, lv.trig, lv.m, S, i, k, e, ep, (lds_u8*)warea, st, err_or, r,
+                                  draws, lregen, hook);
+    }
+    run_epilogue<AR, true>(S, live, i, g0 + i, e, ep, nullptr, r, draws, lregen, st.tstep, eq, stats,
+                           slot);
+    // this wave's stores first, then the chunks' counters: the lane that takes its env's chunk
+    // to 0 hands the chunk to the wave (classified for t + 1 below, in lane order)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    int old = 0;
+    if (live) old = atomicSub(&f.outst[i >> 6], 1);
+    if (live) FLOW_EV_LANE(3, item, (uint32_t)i, (uint32_t)old, (uint32_t)lane | ((uint32_t)mcnt << 8) | ((uint32_t)x << 16));
+    unsigned long long ready = __ballot(live && old == 1);
+    if (lane == 0) FLOW_EV(7, item, (uint32_t)__popcll(ready), (uint32_t)mcnt, x);
+    cl = (int)(i >> 6);
+    return ready;
   };
 
   // The wave's work loop: one unit of work per iteration, chosen by wave-uniform values only

@@ -1,7 +1,7 @@
 // tg_kernels.h — the batch kernels: creation and reset, the one-pass and the two-pass step,
 // k_regen, the flow mode's census and check, and the small per-env queries.  Compiled by
-// tg_amd.hip only, whose host code launches them; the device helpers they share with k_flow are
-// tg_dev.h's.
+// tg_amd.hip only, whose host code launches them.  One env's step is tg_dev.h's, shared with k_flow:
+// step_env (k_step); classify_env, none_rows, lane_groups (k_classify); run_listed, run_epilogue (k_run).
 #pragma once
 #include "tg_dev.h"
 #include "tg_flow.h"
@@ -100,9 +100,9 @@ __global__ __launch_bounds__(BLOCK) void k_step(Soa S, int64_t n, Level L,
                                                  unsigned long long* __restrict__ ks) {
   const unsigned long long kt0 = kst_begin(ks);
   __shared__ __attribute__((aligned(16))) uint8_t win[(BLOCK / 64) * WIN_WAVE_BYTES];
-  LEVEL_IN_LDS();
+  const LevelView lv = level_in_lds(grid, L);
   lds_u8* const wscr = (lds_u8*)win + (threadIdx.x >> 6) * WIN_WAVE_BYTES;
-  step_env<AUTORESET, FINAL, POL>(S, n, L, trig, m, wscr, (int64_t)blockIdx.x * BLOCK + threadIdx.x,
+  step_env<AUTORESET, FINAL, POL>(S, n, L, lv.trig, lv.m, wscr, (int64_t)blockIdx.x * BLOCK + threadIdx.x,
                                   io, q, g0, stats, err_or);
   kst_end(ks, kt0);
 }
@@ -114,7 +114,7 @@ __global__ __launch_bounds__(BLOCK) void k_step(Soa S, int64_t n, Level L,
 // workgroup in LDS and the counters are sharded 8 ways (blockIdx % 8) across cache lines (one
 // word alone saturates at ~88 atomics/us, MI355X_MICROARCH.md "dequeue").
 // Pass 2, k_run: wave w runs chunk w (64 envs) of the worklists concatenated in run order
-// (options in kOrder, each option's 8 shards).  Only the options are padded to whole chunks
+// (options in kRunOrder, each option's 8 shards).  Only the options are padded to whole chunks
 // (round 2 padded every shard), so every wave holds ONE option: a wave-uniform k selects a loop
 // specialised to that option's primitive actions.  (Round 3 also tried worklists per (option,
 // predicted length class), which raised lane efficiency from 0.53 to 0.84 but ran 2-5 % slower:
@@ -124,14 +124,8 @@ __global__ __launch_bounds__(BLOCK) void k_step(Soa S, int64_t n, Level L,
 // ticks are the slowest in wall time (~2,100 cycles each) and which end the kernel, then the
 // long go walks (mean 56 ticks), drops, ladders, interact.  A/B against go
 // first: 0.1366 vs 0.1400 ms.
-__constant__ int kOrder[NLIST] = {O_JUMP_LEFT, O_JUMP_RIGHT, O_GO_LEFT,     O_GO_RIGHT,
-                                  O_DOWN_LEFT, O_DOWN_RIGHT, O_UP_LADDER,   O_DOWN_LADDER,
-                                  O_INTERACT,  L_RESET};
-__constant__ int kSegBase[NLIST] = {kRunPos.of[0] * WSHARDS, kRunPos.of[1] * WSHARDS,
-                                      kRunPos.of[2] * WSHARDS, kRunPos.of[3] * WSHARDS,
-                                      kRunPos.of[4] * WSHARDS, kRunPos.of[5] * WSHARDS,
-                                      kRunPos.of[6] * WSHARDS, kRunPos.of[7] * WSHARDS,
-                                      kRunPos.of[8] * WSHARDS, kRunPos.of[9] * WSHARDS};
+// (the table is tg_dev.h's kRunOrder: the kernels index it per lane, so from constant memory)
+__constant__ RunOrder kRun = kRunOrder;
 
 // 8 waves per SIMD: its 98-106 SGPRs (the level, the step's pointers) held it to 7; forced, 32-55
 // of them spill to VGPR lanes (no VGPR spills, 60 VGPRs).  A/B r04r: uniform 0.1246 vs 0.1258 ms
@@ -152,7 +146,6 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   } lds;
   LdsLevel& lv = lds.lv;
   double* const ostage = lds.ostage;
-  double orow[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
   const bool live = i < n;
   const int lane = threadIdx.x & 63;
@@ -163,67 +156,35 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   double2 a2 = make_double2(0.0, 0.0);
   int2 ep = make_int2(0, 0);
   if (live) {
-    s4 = S.st4[i];
+    load_env<false>(S.st4, S.ang, S.ep, i, s4, a2, ep);
     if constexpr (POL < 0) act = io.actions[i];
-    a2 = S.ang[i];
-    ep = S.ep[i];
   }
   if (threadIdx.x < NLIST) bcnt[threadIdx.x] = 0;
   if (blockIdx.x == 0)
     for (int c = threadIdx.x; c < NCTR; c += BLOCK) w.ctr_next[c * CTR_STRIDE] = 0;
-  stage_level(lv, grid, L);  // includes the barrier
+  stage_cells(lv.grid, lv.trig, grid, L);  // includes the barrier
   const Map m{reinterpret_cast<const uint8_t*>(lv.grid), L.W, L.H};
-  int k = -1;
-  bool runs = false;
   Env e;
   e.mti = 0u;
-  if (live) {
-    unpack_st4(s4, e);
-    if constexpr (POL >= 0) {  // the rollout's on-device policy (tg_rollout)
-      act = policy_action(L, m, e, POL, io.a0, g0 + i, io.t);
-      if (io.actions) io.actions[i] = act;
-    }
-    k = option_index(act);
-    runs = k >= 0 && can_run(L, m, e, k);
-    if (k < 0) e.f |= E_ACTION;
-  }
+  if (live) unpack_st4(s4, e);
+  // the env's worklist (L_RESET's envs are reset in k_run); its stale half, for the refill list
+  const auto [runs, rst, stale, bk] = classify_env<AUTORESET, POL>(L, m, e, live, act, io, i, g0 + i);
   // every env's valid row, coalesced (reward None unless its option runs; k_run writes the
   // listed envs' other rows)
   if (live) io.valid[i] = (uint8_t)runs;
-  // entering done with auto-reset on and no option to run: reset in k_run (L_RESET)
-  const bool rst = AUTORESET && live && !runs && is_done(e);
-  const int bk = runs ? k : rst ? L_RESET : -1;  // the env's worklist
-  // halves left stale and not listed yet go on this step's refill list (MT_LISTED); k_regen
-  // regenerates the lists of several steps at once (a lane that needs a half first does it
-  // itself: the ring leaves >= ~2,400 draws of slack, launch_step)
-  // (dense lists: a drain of a few steps' lists spreads one half per wave, where the per-wave
-  // regions of round 4 left a wave with the few regions holding 3-4 halves for ~0.1 ms; one
-  // atomic per workgroup, beside the worklists' below: per wave, ~2,000 returning atomics per
+  // (dense refill lists: a drain of a few steps' lists spreads one half per wave, where the
+  // per-wave regions of round 4 left a wave with the few regions holding 3-4 halves for ~0.1 ms;
+  // one atomic per workgroup, beside the worklists' below: per wave, ~2,000 returning atomics per
   // counter and step at the masked policy's rate serialised k_classify, 30.8 -> 39.2 us)
-  const bool stale = live && (e.mti & (MT_STALE | MT_LISTED)) == MT_STALE;
-  int srank = 0;
-  {
-    const unsigned long long b = __ballot(stale);
-    srank = __popcll(b & ((1ull << lane) - 1ull));
-    if (lane == 0) rwc[threadIdx.x >> 6] = __popcll(b);
-    if (stale) e.mti |= MT_LISTED;
-  }
-  // workgroup-local slots: one LDS atomic per wave and option present in the wave (the
-  // wave's lanes are matched option by option)
+  const unsigned long long sb = __ballot(stale);
+  const int srank = __popcll(sb & ((1ull << lane) - 1ull));
+  if (lane == 0) rwc[threadIdx.x >> 6] = __popcll(sb);
+  // workgroup-local slots: one LDS atomic per wave and list present in the wave, by the
+  // group's first lane
+  const auto [rank, lead, nb] = lane_groups(bk);
   int slot = 0;
-  {
-    unsigned long long pend = __ballot(bk >= 0);
-    while (pend) {
-      const int first = __ffsll((long long)pend) - 1;
-      const int b0 = __builtin_amdgcn_readlane(bk, first);
-      const unsigned long long b = __ballot(bk == b0);
-      int base = 0;
-      if (lane == first) base = atomicAdd(&bcnt[b0], __popcll(b));
-      base = __shfl(base, first, 64);
-      if (bk == b0) slot = base + __popcll(b & ((1ull << lane) - 1ull));
-      pend &= ~b;
-    }
-  }
+  if (bk >= 0 && lane == lead) slot = atomicAdd(&bcnt[bk], nb);
+  slot = __shfl(slot, lead, 64) + rank;
   __syncthreads();
   // the workgroup's worklist ranges: issue the global atomics now, use them after the
   // reward-None envs are finished (their latency overlaps that work)
@@ -231,7 +192,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   int my_base = 0;
   if (threadIdx.x < NLIST) {
     const int c = bcnt[threadIdx.x];
-    my_base = c ? atomicAdd(&w.ctr[(kSegBase[threadIdx.x] + wshard) * CTR_STRIDE], c) : 0;
+    my_base = c ? atomicAdd(&w.ctr[(kRun.seg_base[threadIdx.x] + wshard) * CTR_STRIDE], c) : 0;
   } else if (threadIdx.x == 64) {  // (another wave than the worklists' atomics)
     int c = 0;
 #pragma unroll
@@ -243,24 +204,12 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   // envs whose option cannot run: reward None, state unchanged (TG/:91-96, OP/:22-23); not
   // done, or auto-reset off (the others are k_run's, L_RESET)
   const bool fin = live && !runs && !rst;
-  if (fin) {
-    e.ang0 = a2.x;
-    e.ang1 = a2.y;
-    Rng rng(S.mt + i * MT_STORE, e.mti, S.mc + i * MT_CODES);  // no draws without a reset
-    StepResult r{0, 0, (int)is_done(e), 0};
-    finish_step<false, FINAL, false>(L, e, rng, i, r, ep, io, orow);
-    if (e.f & E_MASK) atomicOr(err_or, e.f & E_MASK);
-  }
-  const int2 ep_in = ep;
-  store_obs_wave(io.obs, i - lane, __ballot(fin), orow, ostage + (threadIdx.x & ~63) * 9);
+  none_rows<FINAL>(L, S, fin, e, a2, i, ep, io, ostage + (threadIdx.x & ~63) * 9, err_or);
   if (fin) {
     const uint4 s4n = pack(e);
     if (s4n.x != s4.x || s4n.y != s4.y || s4n.z != s4.z || s4n.w != s4.w) {  // reset / flag
-      S.st4[i] = s4n;
-      S.ang[i] = make_double2(e.ang0, e.ang1);
+      S.st4[i] = s4n;  // (reward None: the angles, the return and the episode's start step stay)
     }
-    // reward None: the return and the episode's start step are unchanged unless it ended
-    if (ep.x != ep_in.x || ep.y != ep_in.y) S.ep[i] = ep;
   }
   if (threadIdx.x < NLIST) bbase[threadIdx.x] = my_base;
   if (threadIdx.x == 64) rbase = my_base;
@@ -268,10 +217,10 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   if (stale) {
     int at = rbase + srank;
     for (int v = 0; v < (int)(threadIdx.x >> 6); ++v) at += rwc[v];
-    w.refill[shard * w.rcap + at] = (uint32_t)i | (mt_half(e.mti & MT_POS_MASK) ? 0x80000000u : 0u);
+    w.refill[shard * w.rcap + at] = refill_entry(i, e.mti);
   }
   if (bk >= 0) {
-    const int64_t at = (int64_t)(kSegBase[bk] + wshard) * w.shard_cap + bbase[bk] + slot;
+    const int64_t at = (int64_t)(kRun.seg_base[bk] + wshard) * w.shard_cap + bbase[bk] + slot;
     w.lists[at] = (int32_t)i;
     w.wst4[at] = s4w;
     w.wang[at] = a2;
@@ -331,13 +280,13 @@ __global__ __launch_bounds__(RUN_BLOCK) void k_run(Soa S, int64_t n, Level L,
     ostart[NLIST] = acc;
     oraw[NLIST] = pre[NSEG];
   }
-  RUN_LEVEL_IN_LDS();  // includes the barrier (ostart / oraw)
+  const LevelView lv = run_level_in_lds<RUN_BLOCK, WIN_WAVE_BYTES>(grid, L);  // (the barrier: ostart / oraw)
   const int total = ostart[NLIST];
   const int base = (blockIdx.x * RUN_BLOCK + threadIdx.x) & ~63;  // wave w runs chunk w
   int oj = 0;  // ostart[oj] <= base < ostart[oj + 1] (wave-uniform)
   while (oj + 1 < NLIST && ostart[oj + 1] <= base) ++oj;
   oj = __builtin_amdgcn_readfirstlane(oj);
-  const int k = kOrder[oj];
+  const int k = kRun.list[oj];
   // this lane's place in option k's lists (the raw prefix's coordinates), and its segment
   const int qraw = oraw[oj] + base + (threadIdx.x & 63) - ostart[oj];
   const bool live = base < total && qraw < oraw[oj + 1];
@@ -357,41 +306,19 @@ __global__ __launch_bounds__(RUN_BLOCK) void k_run(Soa S, int64_t n, Level L,
   int2 ep = make_int2(0, 0);
   uint32_t draws = 0;
   int lregen = 0;  // halves this lane regenerated in its option loop
-  lds_u8* const wscr = (lds_u8*)win + (threadIdx.x >> 6) * WIN_WAVE_BYTES;
+  lds_u8* const wscr = (lds_u8*)lv.win + (threadIdx.x >> 6) * WIN_WAVE_BYTES;
   RunStamp stamp;  // the diagnostic build's per-wave timing (tg_run_diag.h): no code in the product
   stamp.begin();
   if (live) {
     const int64_t at = (int64_t)seg * w.shard_cap + idx;
     i = w.lists[at];
-    unpack(w.wst4[at], w.wang[at], e);
-    ep = w.wep[at];
-    RngCodes rng(S.mt + i * MT_STORE, S.mc + i * MT_CODES, e.mti, wscr);
-    rng.prime();  // issue the code loads now; the first draw comes after the policy setup
-    stamp.env_loaded();
-    if (k != O_GO_LEFT && k != O_GO_RIGHT && k != O_INTERACT) __builtin_amdgcn_s_setprio(PRIO_SLOW);
-    // k is wave-uniform: one specialised loop; L_RESET's envs run none (reward None)
-    if (k != L_RESET) run_option(L, trig, m, e, k, rng, r);
-    stamp.option_done(rng.clk);
-    r.done = is_done(e);
-    rng.drain();  // before the first result store: no wait for the window stands behind them
-    finish_step<AUTORESET, FINAL, false>(level_div(L), e, rng, i, r, ep, io);  // valid: k_classify's
-    e.mti = rng.finish();  // a half left here: MT_STALE, listed by the next k_classify
-    draws = rng.draws;
-    lregen = (int)rng.regens;
-    if (e.f & E_MASK) atomicOr(err_or, e.f & E_MASK);
+    load_env<false>(w.wst4, w.wang, w.wep, at, e, ep);
+    run_listed<AUTORESET, FINAL, false>(L, lv.trig, lv.m, S, i, k, e, ep, wscr, io, err_or, r, draws,
+                                        lregen, stamp);
   }
-  // (k_run's grid has BLOCK / RUN_BLOCK workgroups per stats slot, as wave_stats below)
-  if (AUTORESET)
-    record_episodes(live && r.done, g0 + i, ep, io.tstep, q, stats, (int64_t)blockIdx.x / (BLOCK / RUN_BLOCK));
-  if (live) {
-    S.st4[i] = pack(e);
-    S.ang[i] = make_double2(e.ang0, e.ang1);
-    S.ep[i] = ep;
-  }
-  __builtin_amdgcn_s_setprio(0);
-  wave_stats(stats, 0, 0, r.ticks, (int)draws, AUTORESET ? (live && r.done) : 0,
-             __ballot(lregen != 0) ? wave_sum(lregen) : 0, true,
-             (int64_t)blockIdx.x / (BLOCK / RUN_BLOCK));
+  // (k_run's grid has BLOCK / RUN_BLOCK workgroups per stats slot)
+  run_epilogue<AUTORESET, false>(S, live, i, g0 + i, e, ep, nullptr, r, draws, lregen, io.tstep, q, stats,
+                                 (int64_t)blockIdx.x / (BLOCK / RUN_BLOCK));
   kst_end(ks, kt0);
   stamp.wave_end(live, k, r.ticks, (int)((blockIdx.x * RUN_BLOCK + threadIdx.x) >> 6));
 }
@@ -504,8 +431,7 @@ __global__ void k_flow_check(const int32_t* __restrict__ ctl, int P, int32_t C,
 __global__ __launch_bounds__(BLOCK) void k_mask(Soa S, int64_t n, Level L,
                                                  const uint32_t* __restrict__ grid,
                                                  uint16_t* __restrict__ out) {
-  LEVEL_IN_LDS();
-  (void)trig;
+  const Map m = level_in_lds(grid, L).m;
   const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
   if (i >= n) return;
   Env e;
@@ -530,7 +456,7 @@ __global__ __launch_bounds__(BLOCK) void k_actions(Soa S, int64_t n, Level L,
                                                     uint64_t a0, int64_t g0, int64_t t,
                                                     int policy, int32_t* __restrict__ out) {
   __shared__ LdsLevel lv;
-  if (policy == TG_POLICY_MASKED) stage_level(lv, grid, L);  // uniform branch
+  if (policy == TG_POLICY_MASKED) stage_cells(lv.grid, lv.trig, grid, L);  // uniform branch
   const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
   if (i >= n) return;
   const Map m{reinterpret_cast<const uint8_t*>(lv.grid), L.W, L.H};
@@ -556,7 +482,7 @@ __global__ __launch_bounds__(BLOCK) void k_policy_mlp(Soa S, int64_t n, Level L,
                                                        float* __restrict__ value,
                                                        float* __restrict__ logits) {
   __shared__ LdsLevel lv;
-  if (masked) stage_level(lv, grid, L);  // uniform branch
+  if (masked) stage_cells(lv.grid, lv.trig, grid, L);  // uniform branch
   const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
   if (i >= n) return;
   const Map m{reinterpret_cast<const uint8_t*>(lv.grid), L.W, L.H};
@@ -612,8 +538,7 @@ __global__ __launch_bounds__(BLOCK) void k_predicates(Level L, const uint32_t* _
                                                        int x0, int x1, int y0, int y1,
                                                        uint32_t door_bits,
                                                        uint8_t* __restrict__ out) {
-  LEVEL_IN_LDS();
-  (void)trig;
+  const Map m = level_in_lds(grid, L).m;
   const int64_t w = x1 - x0;
   const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
   if (i >= w * (int64_t)(y1 - y0)) return;

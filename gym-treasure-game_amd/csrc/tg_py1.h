@@ -161,11 +161,6 @@ __device__ __forceinline__ void py_ring_cold(uint32_t* W, const tg_pystate* py) 
   lds_twist64(W, W + MT_N);
   lds_twist64(W + MT_N, W + 2 * MT_N);
 }
-__device__ __forceinline__ void py_level(LdsLevel& lv, const Level& L, const uint32_t* __restrict__ grid) {
-  const int nwords = ((L.W + 2 * PAD) * (L.H + 2 * PAD) + 3) / 4;
-  for (int i = threadIdx.x; i < nwords; i += 64) lv.grid[i] = grid[i];
-  if (threadIdx.x < 12) lv.trig[threadIdx.x] = L.trig[threadIdx.x >> 1][threadIdx.x & 1];
-}
 // The Python stream's generation and its two successors, kept on the device between calls
 // (tg_batch::pyc, generation j in slot j): cache_in is it when the caller's state is the one the
 // last call returned (the host compares them), else null and the ring is built from the
@@ -182,7 +177,7 @@ __global__ __launch_bounds__(64) void k_py1(Soa S, Level L, const uint32_t* __re
   __shared__ uint32_t W[PY_GENS * MT_N];
   __shared__ LdsLevel lv;
   const int lane = threadIdx.x;
-  py_level(lv, L, grid);
+  stage_cells<64>(lv.grid, lv.trig, grid, L);
   if (cache_in) {
     for (int i = lane; i < PY_GENS * MT_N; i += 64) W[i] = cache_in[i];
     __syncthreads();
@@ -231,9 +226,7 @@ __global__ __launch_bounds__(64) void k_serve1(Soa Sg, Level Lg, const uint32_t*
   __shared__ uint32_t mk_l[MK_MAX_WORDS];  // the level bitmasks (Map::mk), as k_run's
   extern __shared__ __attribute__((aligned(16))) uint8_t srv_dyn[];
   const int lane = threadIdx.x;
-  py_level(lv, Lg, grid);
-  if (Lg.masks)
-    for (int i = lane; i < mk_words(Lg.W, Lg.H); i += 64) mk_l[i] = Lg.masks[i];
+  stage_cells<64>(lv.grid, lv.trig, grid, Lg, mk_l);
   const uint32_t* const mk = Lg.masks ? mk_l : nullptr;
   Level L = Lg;
   if (stage & SRV_STAGE_GOTAB) {

@@ -100,5 +100,10 @@ struct RunStamp {
   __device__ __forceinline__ void wave_end(bool, int, int, int) const {}
 };
 #endif
+// run_listed's hook where nothing is stamped (k_flow), in every build
+struct NoRunHook {
+  __device__ __forceinline__ void env_loaded() {}
+  __device__ __forceinline__ void option_done(const RunPhaseClock&) {}
+};
 
 }  // namespace
