@@ -605,7 +605,9 @@ class TreasureGameVec:
             if a.shape != shapes[k]:
                 raise ValueError("state[%r] has shape %s, expected %s" % (k, a.shape, shapes[k]))
             arrs[k] = a
-        torch.cuda.synchronize(self.device)
+        # (no synchronisation here: tg_write_state stops a resident N = 1 server first and
+        # synchronises the device itself before it writes; waiting here would wait for that
+        # server to leave by its idle limit)
         check(self._L.tg_write_state(self.handle, *[arrs[k].ctypes.data_as(ctypes.c_void_p)
                                                     if k in arrs else None
                                                     for k in self.STATE_KEYS]), "tg_write_state")

@@ -292,15 +292,43 @@ int tg_probe_dispatch(int32_t kernels, int32_t blocks, void *stream);
  * pos int32 [N][2], flags u32 [N], objs int32 [N][4] (key cx,cy, gold cx,cy),
  * ang f64 [N][2], mt u32 [N][624], mt_pos u32 [N], ep int32 [N][2] (auto-reset episode
  * return, length so far).  Any pointer may be NULL.
- * (mt, mt_pos) is the env's random.getstate() equivalent: the current MT19937 generation and
- * the index into it (CPython's state right after a twist, index 0..623). */
+ *
+ * flags: one word per env,
+ *   bits 0..4    jump_ticker (0..23)
+ *   bit  5       facing_right
+ *   bit  6 + i   the boolean of interactive object i, in the order doors, handles, bolt, each
+ *                kind in the order of the objects file: door.closed at bits 6..8, handle.up at
+ *                bits 9..10, bolt.locked at bit 11
+ *   bits 12..14  len(player_bag) (0..7)
+ *   bit  15 + j  item j of player_bag, j = 0 the first one picked up: 1 = the gold coin, 0 = the
+ *                key; 0 for j >= len(player_bag)
+ *   bits 22..23  not used, 0
+ *   bits 24..31  the env's TG_ERR_* bits (sticky: a reset keeps them; 0 in a healthy env)
+ * objs: the cells the reference keeps in key.cx, key.cy, goldcoin.cx, goldcoin.cy (an item in
+ * the bag lies in the bottom row, a used key at (-1, -1)); each fits an int8.
+ * ang: handle.angle of the level's two handles, in the order of the objects file.
+ * ep: the unfinished episode of the env, as tg_episode counts a finished one: ep[i][0] is the
+ * sum of the step rewards (None counts 0) and ep[i][1] the number of env-steps, valid or not,
+ * since the env's last reset (tg_reset, tg_reset1 or the auto-reset of a step that returned
+ * done; the constructor's state before any step: 0, 0).  A step that returns done without
+ * TG_STEP_AUTORESET counts like any other, so (0, 0) holds right after a reset only.
+ * (mt, mt_pos) is the env's random.getstate() equivalent: the MT19937 generation holding the
+ * env's next word and the index of that word in it, always even (a random() takes two words)
+ * and in 0..622.  Where CPython holds (generation, 624), "twist before the next word" -- the
+ * state after the last word of a generation -- this call reports the same stream position as
+ * (the twisted successor generation, 0); random.setstate() accepts either form and continues
+ * identically. */
 int tg_read_state(tg_batch *h, int32_t *pos, uint32_t *flags, int32_t *objs, double *ang,
                   uint32_t *mt, uint32_t *mt_pos, int32_t *ep);
 /* Checkpoint restore, the inverse of tg_read_state (host buffers, synchronises): every env
  * continues bit-exactly from the given state.  All pointers but ep are required (ep NULL =
- * zeros); mt_pos must be even and <= 624 (this path's draws consume words in pairs; 624 =
- * CPython's "twist before the next draw"), i.e. any random.getstate() of the reference env
- * reached through step()/reset().  The episode queue and counters are not touched. */
+ * zeros); mt_pos must be even and in 0..624 (this path's draws consume words in pairs; 624 =
+ * CPython's "twist before the next draw", the same position as the successor generation at 0),
+ * i.e. any random.getstate() of the reference env reached through step()/reset(), and what
+ * tg_read_state returns (0..622).  pos must fit an int16 and objs an int8 each.  ep is the
+ * (return, length) pair of tg_read_state: the next finished episode of the env reports them
+ * plus its steps after the restore.  A call that fails (TG_E_INVAL) has changed nothing.  The
+ * episode queue and counters are not touched. */
 int tg_write_state(tg_batch *h, const int32_t *pos, const uint32_t *flags, const int32_t *objs,
                    const double *ang, const uint32_t *mt, const uint32_t *mt_pos,
                    const int32_t *ep);
