@@ -32,7 +32,7 @@ int grid_for(int64_t n) { return (int)((n + BLOCK - 1) / BLOCK); }
 // at most n/64 + NLIST chunks (idle blocks interleaved among the option blocks, so that MT
 // regenerations start at once, measured no faster for the masked policy and slower for the
 // uniform one: DESIGN.md §3.3)
-int run_grid_for(int64_t n) { return grid_for(n) + (NLIST * 64 + BLOCK - 1) / BLOCK; }
+int run_grid_for(int64_t n) { return grid_for(n) + (RUN_EXTRA + BLOCK - 1) / BLOCK; }
 // one launch-counter slot per workgroup of the widest step launch (k_run)
 int stat_slots(int64_t n) { return run_grid_for(n); }
 
@@ -126,13 +126,16 @@ int alloc_ctx(StepCtx& c, int64_t off, int64_t n) {
   c.rcap = (int64_t)((grid_for(n) + SHARDS - 1) / SHARDS) * BLOCK * REGEN_STEPS;
   ALLOC(c.refill, sizeof(uint32_t) * SHARDS * (size_t)c.rcap);
   ALLOC(c.regen_ctr, sizeof(int32_t) * 2 * RCTR_N * CTR_STRIDE);
+  // a quiet list holds one step's entries: drained by the k_run of the step that appended them
+  c.qcap = (int64_t)((grid_for(n) + SHARDS - 1) / SHARDS) * BLOCK;
+  ALLOC(c.quiet, sizeof(uint32_t) * SHARDS * (size_t)c.qcap);
   HIP_TRY(hipMemset(c.stats, 0, sizeof(unsigned long long) * ST_COUNT * (size_t)stat_slots(n)));
   HIP_TRY(hipMemset(c.wctr, 0, sizeof(int32_t) * 2 * NCTR * CTR_STRIDE));
   HIP_TRY(hipMemset(c.regen_ctr, 0, sizeof(int32_t) * 2 * RCTR_N * CTR_STRIDE));
   return TG_OK;
 }
 void free_ctx(StepCtx& c) {
-  void* bufs[] = {c.stats, c.wl, c.wst4, c.wang, c.wep, c.wctr, c.refill, c.regen_ctr};
+  void* bufs[] = {c.stats, c.wl, c.wst4, c.wang, c.wep, c.wctr, c.refill, c.regen_ctr, c.quiet};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (c.ev) (void)hipEventDestroy(c.ev);
@@ -244,7 +247,7 @@ int launch_step(tg_batch* h, StepCtx& c, const StepIO& io_in, bool ar, hipStream
     // the set the next k_regen reads
     const Work w{c.wl,     c.wst4, c.wang, c.wep, cur, nxt, c.refill,
                  c.regen_ctr + (c.regen_parity * RCTR_N + RCTR_LIST) * CTR_STRIDE, c.rcap,
-                 c.shard_cap};
+                 c.shard_cap, c.quiet, c.qcap};
     const auto kc = step_inst(ar, fo, io.policy,
                               [](auto AR, auto FO, auto POL) { return &k_classify<AR, FO, POL>; });
     const auto kr = step_inst(ar, fo, -1, [](auto AR, auto FO, auto) { return &k_run<AR, FO>; });
@@ -1368,6 +1371,7 @@ int tg_get_stats(tg_batch* h, tg_stats* out) {
   out->launches = out->steps / (h->n ? h->n : 1);
   out->kernel_ms = h->kernel_ms_done;
   out->regens = (int64_t)s[ST_REGENS] * MT_HALF_GENS;  // halves -> generations
+  out->regens_quiet = (int64_t)s[ST_RQUIET] * MT_HALF_GENS;
   out->wave_ticks = (int64_t)s[ST_WTICKS];
   out->timed_launches = h->timed_launches;
   out->run_ms = h->run_ms_done;

@@ -91,10 +91,12 @@ struct StepCtx {
   uint4* wst4 = nullptr;   // the listed envs' state in worklist order (k_classify -> k_run)
   double2* wang = nullptr;
   int2* wep = nullptr;
-  int32_t* wctr = nullptr; // sharded counters, two sets (step parity)
+  int32_t* wctr = nullptr; // sharded counters (worklists, quiet lists), two sets (step parity)
   uint32_t* refill = nullptr;  // stale MT halves listed by k_classify: SHARDS lists (k_regen)
   int64_t rcap = 0;            // entries per list: a shard's envs x REGEN_STEPS
   int64_t shard_cap = 0;
+  uint32_t* quiet = nullptr;   // this step's quiet envs' stale halves: SHARDS lists (k_run's drain)
+  int64_t qcap = 0;            // entries per list: a shard's envs
   int parity = 0;  // which half of wctr this compact step counts in
   int rpend = 0;   // compact steps whose refill lists k_regen has not drained
   int32_t* regen_ctr = nullptr;  // per XCD: k_regen's grab counters and the lists' lengths, two

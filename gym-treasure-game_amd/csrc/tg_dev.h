@@ -106,11 +106,17 @@ __device__ __forceinline__ LevelView level_in_lds(const uint32_t* __restrict__ g
 // 0: 16-B aligned for the LDS-DMA), then the level's grid words and bitmasks (Map::mk); includes
 // the barrier.  (Sized at launch for the handle's level instead of the largest, with the rows'
 // loads issued before the staging barrier, it measured ~4 % slower for the masked: DESIGN.md §3.1.)
+// (run_lds_win: the waves' areas alone, nothing staged and no barrier: k_run's workgroups past
+// every listed chunk, whose waves twist in theirs)
+template <int NT, int WAVE_BYTES>
+__device__ __forceinline__ uint8_t* run_lds_win() {
+  __shared__ uint4 run_lds[((NT / 64) * WAVE_BYTES + MAX_CELLS + 4 * MK_MAX_WORDS) / 16];
+  return reinterpret_cast<uint8_t*>(run_lds);
+}
 template <int NT, int WAVE_BYTES>
 __device__ __forceinline__ LevelView run_level_in_lds(const uint32_t* __restrict__ grid, const Level& L) {
-  __shared__ uint4 run_lds[((NT / 64) * WAVE_BYTES + MAX_CELLS + 4 * MK_MAX_WORDS) / 16];
   __shared__ uint32_t ltrig[12];
-  uint8_t* const win = reinterpret_cast<uint8_t*>(run_lds);
+  uint8_t* const win = run_lds_win<NT, WAVE_BYTES>();
   uint32_t* const lgrid = reinterpret_cast<uint32_t*>(win + (NT / 64) * WAVE_BYTES);
   uint32_t* const lmk = lgrid + grid_words(L.W, L.H);
   stage_cells<NT>(lgrid, ltrig, grid, L, lmk);
@@ -492,6 +498,7 @@ __device__ __forceinline__ int wave_sum(int v) {
 }
 
 enum { ST_STEPS, ST_VALID, ST_TICKS, ST_DRAWS, ST_EPISODES, ST_EP_OVERFLOW, ST_REGENS, ST_WTICKS,
+       ST_RQUIET,  // of ST_REGENS, the halves of k_run's quiet drain
        ST_COUNT };
 
 // 64-lane max (wave64)
@@ -812,8 +819,17 @@ constexpr RunOrder make_run_order() {
 constexpr RunOrder kRunOrder = make_run_order();
 constexpr int NSEG = NLIST * WSHARDS;  // segment = run position * WSHARDS + shard
 static_assert(NSEG <= 2 * RUN_BLOCK, "k_run's prefix: two segments per thread");
-constexpr int NCTR = NSEG;      // the worklist counters
+// the step's counters: the worklists', then the quiet lists' lengths (one per shard)
+constexpr int QCTR = NSEG;
+constexpr int NCTR = NSEG + SHARDS;
 constexpr int CTR_STRIDE = 32;  // counters 128 B apart
+// k_run's grid covers the envs rounded up to a k_classify workgroup plus RUN_EXTRA lanes, and
+// its chunk space ends at or before listed + NLIST * 63 (each list padded to whole chunks) <=
+// n + NLIST * 63 < the grid's lanes; both are whole waves, so at least one wave of every k_run
+// grid has no chunk, at every batch size: the quiet lists are always drained (k_run)
+constexpr int RUN_EXTRA = NLIST * 64;
+static_assert(RUN_EXTRA > NLIST * 63 && BLOCK % 64 == 0 && RUN_BLOCK % 64 == 0,
+              "a k_run grid always has a wave without a chunk");
 struct Work {
   int32_t* __restrict__ lists;   // [NSEG][shard_cap], segment = run position * WSHARDS + shard
   // the listed envs' state, in worklist order (written by k_classify, which has loaded it
@@ -830,6 +846,11 @@ struct Work {
   int32_t* __restrict__ rcnt;
   int64_t rcap;
   int64_t shard_cap;
+  // the stale halves of this step's quiet envs (live, in no worklist: nothing but k_run's quiet
+  // drain touches them before the next k_classify), one list per shard, one step's entries:
+  // list x at quiet[x * qcap ..], its length at ctr[(QCTR + x) * CTR_STRIDE]
+  uint32_t* __restrict__ quiet;
+  int64_t qcap;
 };
 // k_regen (tg_kernels.h) drains the stale-MT-half refill lists every REGEN_STEPS compact steps
 constexpr int REGEN_STEPS = 16;
@@ -871,6 +892,38 @@ __device__ __forceinline__ EnvClass classify_env(const Level& L, const Map& m, E
 // a refill list's entry: env | source half
 __device__ __forceinline__ uint32_t refill_entry(int64_t i, uint32_t mti) {
   return (uint32_t)i | (mt_half(mti & MT_POS_MASK) ? 0x80000000u : 0u);
+}
+// Up to 64 refill entries, one per lane (mine: this lane holds one, of env env_l), claimed and
+// regenerated by the whole wave: k_regen's and k_run's quiet drain's body.  The claim clears
+// MT_STALE | MT_LISTED in the env's state word by an atomic AND, and the half is regenerated only
+// if that clear found MT_STALE: the half not holding the position, from the last generation of
+// the one holding it.  An env can be listed twice before a drain (its lane regenerated the listed
+// half itself, crossed again, and the next k_classify listed the new stale half): both entries
+// name the half not holding the position, and the second claim finds it clean (round 4
+// regenerated such a half once per entry: 20,320 vs 15,360 halves on the corridor level).
+// Entries of one call for one env are serialised at the word's L2 channel.  Returns the halves
+// regenerated; scr: the wave's WAVE_SCRATCH bytes of LDS.  Every lane of the wave reaches it.
+template <bool NT>
+__device__ __forceinline__ int regen_entries(const Soa& S, bool mine, uint32_t env_l, lds_u32* scr) {
+  uint32_t* const st_w = reinterpret_cast<uint32_t*>(S.st4);  // word 4i + 3: env i's MT word
+  const uint32_t st_l = mine ? atomicAnd(&st_w[(int64_t)env_l * 4 + 3], ~(MT_STALE | MT_LISTED)) : 0u;
+  unsigned long long need = __ballot(mine && (st_l & MT_STALE));
+  int halves = 0;
+  // one half at a time: 52 VGPRs in k_regen, 8 waves per SIMD (the next half's source loads
+  // pipelined into this one's twist took 76 VGPRs, 6 waves, and measured no faster: DESIGN.md §3.3)
+  while (need) {
+    const int L = __ffsll((long long)need) - 1;
+    need &= need - 1;
+    const uint32_t env = __builtin_amdgcn_readlane(env_l, L), s = __builtin_amdgcn_readlane(st_l, L);
+    const uint32_t dst = (uint32_t)MT_HALF - mt_half(s & MT_POS_MASK);
+    uint32_t* const mt = S.mt + (int64_t)env * MT_STORE;
+    TwistIn t;
+    twist_load((const glb_u32*)(mt + regen_src_off(dst)), t);
+    twist_chain<NT>(t, (glb_u32*)mt, S.mc + (int64_t)env * MT_CODES, (int)(dst / (uint32_t)MT_N),
+                    MT_HALF_GENS, true, scr);
+    ++halves;
+  }
+  return halves;
 }
 // the step of the wave's envs whose option cannot run (fin; not L_RESET's): reward None, state
 // unchanged (TG/:91-96, OP/:22-23), the obs rows through the wave's LDS `stage`.  The valid row

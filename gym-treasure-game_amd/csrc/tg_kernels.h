@@ -137,7 +137,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
     unsigned long long* __restrict__ ks) {
   const unsigned long long kt0 = kst_begin(ks);
   __shared__ int bcnt[NLIST], bbase[NLIST];
-  __shared__ int rwc[BLOCK / 64], rbase;  // stale halves per wave; the workgroup's list range
+  // stale halves per wave and the workgroup's list range: the deferred list's (k_regen) and the
+  // quiet list's (this step's k_run)
+  __shared__ int rwc[BLOCK / 64], rbase, qwc[BLOCK / 64], qbase;
   // the obs staging reuses the level's LDS: nothing reads the grid after the second barrier
   // below (finish_step / reset_env use only L), so 18.4 KB instead of 20.8 KB per workgroup
   __shared__ union {
@@ -176,9 +178,17 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   // per-wave regions of round 4 left a wave with the few regions holding 3-4 halves for ~0.1 ms;
   // one atomic per workgroup, beside the worklists' below: per wave, ~2,000 returning atomics per
   // counter and step at the masked policy's rate serialised k_classify, 30.8 -> 39.2 us)
-  const unsigned long long sb = __ballot(stale);
-  const int srank = __popcll(sb & ((1ull << lane) - 1ull));
-  if (lane == 0) rwc[threadIdx.x >> 6] = __popcll(sb);
+  // A stale half of a quiet env (live, bk < 0: no option, no L_RESET) goes on the step's quiet
+  // list: nothing reads or writes that env's state word, ring or codes between this kernel and
+  // the next step's k_classify except the k_run wave that claims the entry.  Any other goes on
+  // the deferred list.
+  const bool quiet = bk < 0;
+  const unsigned long long qb = __ballot(stale && quiet), db = __ballot(stale && !quiet);
+  const int srank = __popcll((quiet ? qb : db) & ((1ull << lane) - 1ull));
+  if (lane == 0) {
+    rwc[threadIdx.x >> 6] = __popcll(db);
+    qwc[threadIdx.x >> 6] = __popcll(qb);
+  }
   // workgroup-local slots: one LDS atomic per wave and list present in the wave, by the
   // group's first lane
   const auto [rank, lead, nb] = lane_groups(bk);
@@ -198,6 +208,11 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
 #pragma unroll
     for (int v = 0; v < BLOCK / 64; ++v) c += rwc[v];
     my_base = c ? atomicAdd(&w.rcnt[shard * CTR_STRIDE], c) : 0;
+  } else if (threadIdx.x == 128) {  // (and a third wave: the quiet list's)
+    int c = 0;
+#pragma unroll
+    for (int v = 0; v < BLOCK / 64; ++v) c += qwc[v];
+    my_base = c ? atomicAdd(&w.ctr[(QCTR + shard) * CTR_STRIDE], c) : 0;
   }
   const uint4 s4w = pack(e);  // the state the worklist copy carries (listed half, E_ACTION)
 
@@ -213,11 +228,12 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   }
   if (threadIdx.x < NLIST) bbase[threadIdx.x] = my_base;
   if (threadIdx.x == 64) rbase = my_base;
+  if (threadIdx.x == 128) qbase = my_base;
   __syncthreads();
   if (stale) {
-    int at = rbase + srank;
-    for (int v = 0; v < (int)(threadIdx.x >> 6); ++v) at += rwc[v];
-    w.refill[shard * w.rcap + at] = refill_entry(i, e.mti);
+    int at = (quiet ? qbase : rbase) + srank;
+    for (int v = 0; v < (int)(threadIdx.x >> 6); ++v) at += quiet ? qwc[v] : rwc[v];
+    (quiet ? w.quiet + shard * w.qcap : w.refill + shard * w.rcap)[at] = refill_entry(i, e.mti);
   }
   if (bk >= 0) {
     const int64_t at = (int64_t)(kRun.seg_base[bk] + wshard) * w.shard_cap + bbase[bk] + slot;
@@ -228,6 +244,63 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   }
   wave_stats(stats, live ? 1 : 0, runs ? 1 : 0, 0, 0, 0);
   kst_end(ks, kt0);
+}
+
+// ---- k_run's quiet drain: the step's quiet lists, by the waves that have no chunk ---------------
+// k_classify lists the stale half of an env that is quiet in this step (live, in no worklist) on
+// the quiet list of its shard.  Between that k_classify and the next step's, a quiet env is touched
+// by nobody else: k_run's option waves read and write listed envs only, and both kernels are
+// ordered on the stream with their neighbours.  So the chunk-less waves of k_run regenerate those
+// halves here, under the option waves' latency chains, with k_regen's per-entry body (claim by the
+// atomic AND, plain ring stores: the ring is read by later launches) at priority 0.
+// Which wave takes which entry is static: the waves from the chunk space's end (`total` lanes) to
+// the grid's end are numbered d = 0 .. nidle - 1, the 8 lists are concatenated, and wave d takes
+// entries [d * grab, (d + 1) * grab), then strides by nidle * grab, with grab the even share (1
+// for a uniform step: ~2,600 entries for > 12,000 such waves; at most 64, one per lane).  So the
+// entries sit on the first chunk-less workgroups, which are dispatched right behind the option
+// workgroups (numbering the waves from the grid's end, or making every 3rd or 5th chunk-less
+// workgroup a draining one, measured slower than the parent: DESIGN.md §3.3).  Every
+// k_run grid has nidle >= 1 (tg_dev.h RUN_EXTRA), and every wave of a grid runs, so every list is
+// empty when the kernel ends, whatever the batch size, with no grab counter: 12,000 waves each
+// probing 8 counters would queue at ~88 atomics / us per word, and nothing here returns a value
+// through an atomic but the claims themselves.
+// pre: k_run's prefix of the worklist counters; base: the wave's first lane in the grid; scr: the
+// wave's code-window area (WAVE_SCRATCH bytes of it).  Returns the halves regenerated.
+__device__ __forceinline__ int quiet_drain(const Soa& S, const Work& w, const int* pre, int base,
+                                           lds_u32* scr, unsigned long long* __restrict__ stats) {
+  __builtin_amdgcn_s_setprio(0);
+  int qp[SHARDS + 1];  // the lists' exclusive prefix (wave-uniform)
+  qp[0] = 0;
+#pragma unroll
+  for (int x = 0; x < SHARDS; ++x) qp[x + 1] = qp[x] + w.ctr[(QCTR + x) * CTR_STRIDE];
+  const int64_t tot = qp[SHARDS];
+  if (!tot) return 0;  // (the masked policy lists every env: nothing is quiet)
+  int total = 0;  // the chunk space's end: every list padded to whole chunks
+  for (int j = 0; j < NLIST; ++j) total += (pre[(j + 1) * WSHARDS] - pre[j * WSHARDS] + 63) & ~63;
+  const int64_t nidle = (int64_t)gridDim.x * (RUN_BLOCK / 64) - (total >> 6);
+  int64_t grab = (tot + nidle - 1) / nidle;
+  if (grab > 64) grab = 64;
+  const int lane = threadIdx.x & 63;
+  int halves = 0;
+  for (int64_t j0 = (int64_t)((base - total) >> 6) * grab; j0 < tot; j0 += nidle * grab) {
+    const int64_t j = j0 + lane;
+    const bool mine = lane < grab && j < tot;
+    uint32_t env_l = 0u;
+    if (mine) {
+      int x = 0, lo = 0;  // qp[x] = lo <= j < qp[x + 1]
+#pragma unroll
+      for (int y = 1; y < SHARDS; ++y)
+        if (j >= qp[y]) x = y, lo = qp[y];
+      env_l = w.quiet[x * w.qcap + (j - lo)] & 0x7FFFFFFFu;
+    }
+    halves += regen_entries<false>(S, mine, env_l, scr);
+  }
+  if (lane == 0 && halves) {  // (k_run's grid has BLOCK / RUN_BLOCK workgroups per stats slot)
+    unsigned long long* const slot = stats + (size_t)(blockIdx.x / (BLOCK / RUN_BLOCK)) * ST_COUNT;
+    atomicAdd(&slot[ST_REGENS], (unsigned long long)halves);
+    atomicAdd(&slot[ST_RQUIET], (unsigned long long)halves);
+  }
+  return halves;
 }
 
 template <bool AUTORESET, bool FINAL>
@@ -263,26 +336,38 @@ __global__ __launch_bounds__(RUN_BLOCK) void k_run(Soa S, int64_t n, Level L,
     if (threadIdx.x == RUN_BLOCK - 1) pre[NSEG] = v;
   }
   __syncthreads();
+  const int base = (blockIdx.x * RUN_BLOCK + threadIdx.x) & ~63;  // wave w runs chunk w
   // a workgroup past every listed chunk (the grid covers n envs, a uniform step lists ~1 in 5;
-  // the options' padding adds < 64 each) leaves before it stages the level: ~3/4 of the grid
-  if ((int)(blockIdx.x * RUN_BLOCK) >= pre[NSEG] + NLIST * 63) {
+  // the options' padding adds < 64 each) does not stage the level: ~3/4 of the grid
+  const bool past = (int)(blockIdx.x * RUN_BLOCK) >= pre[NSEG] + NLIST * 63;
+  LevelView lv{nullptr, Map{nullptr, 0, 0}, run_lds_win<RUN_BLOCK, WIN_WAVE_BYTES>()};
+  if (!past) {
+    if (threadIdx.x == 0) {
+      int acc = 0;
+      for (int j = 0; j < NLIST; ++j) {
+        const int sb = j * WSHARDS, se = sb + WSHARDS;
+        ostart[j] = acc;
+        oraw[j] = pre[sb];
+        acc += (pre[se] - pre[sb] + 63) & ~63;
+      }
+      ostart[NLIST] = acc;
+      oraw[NLIST] = pre[NSEG];
+    }
+    lv = run_level_in_lds<RUN_BLOCK, WIN_WAVE_BYTES>(grid, L);  // (the barrier: ostart / oraw)
+  }
+  lds_u8* const wscr = (lds_u8*)lv.win + (threadIdx.x >> 6) * WIN_WAVE_BYTES;
+  // A wave without a chunk (every wave of a workgroup that is past, and the last listed
+  // workgroup's waves from the chunk space's end on) drains the step's quiet lists instead
+  // (quiet_drain) and leaves: the option waves below never touch those lists.
+  RunStamp stamp;  // the diagnostic build's per-wave timing (tg_run_diag.h): no code in the product
+  stamp.begin();
+  if (past || base >= ostart[NLIST]) {
+    const int halves = quiet_drain(S, w, pre, base, (lds_u32*)wscr, stats);
     kst_end(ks, kt0);
+    stamp.wave_end(false, 0, 0, base >> 6, halves);
     return;
   }
-  if (threadIdx.x == 0) {
-    int acc = 0;
-    for (int j = 0; j < NLIST; ++j) {
-      const int sb = j * WSHARDS, se = sb + WSHARDS;
-      ostart[j] = acc;
-      oraw[j] = pre[sb];
-      acc += (pre[se] - pre[sb] + 63) & ~63;
-    }
-    ostart[NLIST] = acc;
-    oraw[NLIST] = pre[NSEG];
-  }
-  const LevelView lv = run_level_in_lds<RUN_BLOCK, WIN_WAVE_BYTES>(grid, L);  // (the barrier: ostart / oraw)
   const int total = ostart[NLIST];
-  const int base = (blockIdx.x * RUN_BLOCK + threadIdx.x) & ~63;  // wave w runs chunk w
   int oj = 0;  // ostart[oj] <= base < ostart[oj + 1] (wave-uniform)
   while (oj + 1 < NLIST && ostart[oj + 1] <= base) ++oj;
   oj = __builtin_amdgcn_readfirstlane(oj);
@@ -306,9 +391,6 @@ __global__ __launch_bounds__(RUN_BLOCK) void k_run(Soa S, int64_t n, Level L,
   int2 ep = make_int2(0, 0);
   uint32_t draws = 0;
   int lregen = 0;  // halves this lane regenerated in its option loop
-  lds_u8* const wscr = (lds_u8*)lv.win + (threadIdx.x >> 6) * WIN_WAVE_BYTES;
-  RunStamp stamp;  // the diagnostic build's per-wave timing (tg_run_diag.h): no code in the product
-  stamp.begin();
   if (live) {
     const int64_t at = (int64_t)seg * w.shard_cap + idx;
     i = w.lists[at];
@@ -320,12 +402,13 @@ __global__ __launch_bounds__(RUN_BLOCK) void k_run(Soa S, int64_t n, Level L,
   run_epilogue<AUTORESET, false>(S, live, i, g0 + i, e, ep, nullptr, r, draws, lregen, io.tstep, q, stats,
                                  (int64_t)blockIdx.x / (BLOCK / RUN_BLOCK));
   kst_end(ks, kt0);
-  stamp.wave_end(live, k, r.ticks, (int)((blockIdx.x * RUN_BLOCK + threadIdx.x) >> 6));
+  stamp.wave_end(live, k, r.ticks, base >> 6);
 }
 
 // ---- deferred regeneration of the listed stale MT halves (k_regen) ----------------------------
 // k_classify appends the halves the previous step left stale (MT_STALE) to its shard's refill
-// list and marks them MT_LISTED; every REGEN_STEPS compact steps (and on tg_regenerate) k_regen
+// list (those of quiet envs to the step's quiet list instead: k_run's quiet drain, above) and
+// marks them MT_LISTED; every REGEN_STEPS compact steps (and on tg_regenerate) k_regen
 // regenerates every pending entry with a full-occupancy grid and no option loops beside it: the
 // waves of XCD x (blockIdx.x % 8) take list x's entries, an even share each (the halves cost
 // the same: MT_HALF_GENS twists), the rest from the list's counter.  An entry is regenerated iff
@@ -357,11 +440,6 @@ __global__ __launch_bounds__(BLOCK) void k_regen(Soa S, const uint32_t* __restri
   if (blockIdx.x == 0 && threadIdx.x < RCTR_N) ctr_next[threadIdx.x * CTR_STRIDE] = 0;
   int32_t* const q = ctr + xcd * CTR_STRIDE;
   const uint32_t* const list = refill + xcd * rcap;
-  uint32_t* const st_w = reinterpret_cast<uint32_t*>(S.st4);  // word 4i + 3: env i's MT word
-  auto src_of = [&](uint32_t env, uint32_t s) {
-    const uint32_t dst = (uint32_t)MT_HALF - mt_half(s & MT_POS_MASK);
-    return (const glb_u32*)(S.mt + (int64_t)env * MT_STORE + regen_src_off(dst));
-  };
   // this wave's index among its XCD's waves; the first grab is static (an even share, at most
   // 64: one entry per lane), the rest come from the counter, which starts past the static ones
   const int wx = (int)(blockIdx.x >> 3) * (BLOCK / 64) + (int)(threadIdx.x >> 6);
@@ -382,27 +460,7 @@ __global__ __launch_bounds__(BLOCK) void k_regen(Soa S, const uint32_t* __restri
     if (j0 >= cnt) break;
     const int64_t m = cnt - j0 < grab ? cnt - j0 : grab;
     const uint32_t env_l = lane < m ? list[j0 + lane] & 0x7FFFFFFFu : 0u;
-    // claim: clear MT_STALE | MT_LISTED and regenerate only if this lane's clear found
-    // MT_STALE.  An env can be listed twice before a drain (its lane regenerated the listed
-    // half itself, crossed again, and the next k_classify listed the new stale half): both
-    // entries name the half not holding the position, and the second claim finds it clean
-    // (round 4 regenerated such a half once per entry: 20,320 vs 15,360 halves on the corridor
-    // level).  Entries of one grab for one env are serialised at the word's L2 channel.
-    const uint32_t st_l = lane < m ? atomicAnd(&st_w[(int64_t)env_l * 4 + 3], ~(MT_STALE | MT_LISTED)) : 0u;
-    unsigned long long need = __ballot(lane < m && (st_l & MT_STALE));
-    // one half at a time: 52 VGPRs, 8 waves per SIMD (the next half's source loads pipelined
-    // into this one's twist took 76 VGPRs, 6 waves, and measured no faster: DESIGN.md §3.3)
-    while (need) {
-      const int L = __ffsll((long long)need) - 1;
-      need &= need - 1;
-      const uint32_t env = __builtin_amdgcn_readlane(env_l, L), s = __builtin_amdgcn_readlane(st_l, L);
-      const uint32_t dst = (uint32_t)MT_HALF - mt_half(s & MT_POS_MASK);
-      TwistIn t;
-      twist_load(src_of(env, s), t);
-      twist_chain<REGEN_NT>(t, (glb_u32*)(S.mt + (int64_t)env * MT_STORE), S.mc + (int64_t)env * MT_CODES,
-                            (int)(dst / (uint32_t)MT_N), MT_HALF_GENS, true, scr);
-      ++halves;
-    }
+    halves += regen_entries<REGEN_NT>(S, lane < m, env_l, scr);  // claim, then regenerate (tg_dev.h)
   }
   // the grid can exceed the stats slots (>= 8 workgroups, one per XCD counter, at small n)
   if (lane == 0 && halves)

@@ -14,7 +14,7 @@
 //                    4 start, 5 end (s_memrealtime: 100 MHz, chip-wide)
 //                    6 plain walk, 7 window refill, 8 full ticks, 9 rounds: the phase clock of the
 //                      lane whose option loop ran longest (the wave's own time)
-//                    10 always 0 (the queue halves a wave regenerated, until k_regen took them)
+//                    10 the halves an idle wave regenerated in k_run's quiet drain (else 0)
 #pragma once
 
 namespace {  // as the rest of the device layer: each unit its own
@@ -51,7 +51,8 @@ struct RunStamp {
     ph1 = c.ph[1], ph2 = c.ph[2], ph3 = c.ph[3], rounds = c.rounds;
   }
   // wv: the wave's index in the grid; k: its option (wave-uniform); ticks: this lane's
-  __device__ __forceinline__ void wave_end(bool live, int k, int ticks, int wv) const {
+  // halves: an idle wave's quiet drain's
+  __device__ __forceinline__ void wave_end(bool live, int k, int ticks, int wv, int halves = 0) const {
     const unsigned long long t3 = __builtin_amdgcn_s_memtime();
     int mx = ticks, sum = ticks;
     for (int o = 32; o > 0; o >>= 1) {
@@ -85,7 +86,7 @@ struct RunStamp {
       g[7] = p2;
       g[8] = p3;
       g[9] = pr;
-      g[10] = 0;
+      g[10] = (unsigned long long)halves;
     }
   }
 };
@@ -97,7 +98,7 @@ struct RunStamp {
   __device__ __forceinline__ void begin() {}
   __device__ __forceinline__ void env_loaded() {}
   __device__ __forceinline__ void option_done(const RunPhaseClock&) {}
-  __device__ __forceinline__ void wave_end(bool, int, int, int) const {}
+  __device__ __forceinline__ void wave_end(bool, int, int, int, int = 0) const {}
 };
 #endif
 // run_listed's hook where nothing is stamped (k_flow), in every build

@@ -2,7 +2,8 @@
 // (MT_HALF_GENS generations, tg_core.h) twisted by the 64 lanes of one wave, the generations
 // chained in the wave's LDS scratch, every generation's 312 draw codes and the even
 // generations' 624 words stored (tg_core.h MT_STORE).
-// Used by k_regen (the deferred regeneration, every 16 compact steps), k_gen_twist (tg_create,
+// Used by k_regen (the deferred regeneration, every 16 compact steps) and k_run's quiet drain
+// (regen_entries, tg_dev.h), k_gen_twist (tg_create,
 // tg_write_state), k_reset (tg_kernels.h) and k_step (step_env, tg_dev.h).  (The twist variants measured in isolation,
 // DESIGN.md §3.3, are restated in scripts/calib/twist_bench.hip.)
 //

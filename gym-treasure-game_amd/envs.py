@@ -486,6 +486,10 @@ class TreasureGameVec:
         check(self._L.tg_regenerate(self.handle, self._stream()), "tg_regenerate")
 
     def stats(self):
+        """tg_stats as a dict (include/tg_amd.h): counters since creation / ``stats_reset()``,
+        among them ``regens`` (MT generations regenerated, by whichever kernel) and
+        ``regens_quiet`` (of those, the ones k_run's chunk-less waves regenerated in the step
+        that listed them)."""
         s = _lib.Stats()
         check(self._L.tg_get_stats(self.handle, ctypes.byref(s)), "tg_get_stats")
         return s.as_dict()

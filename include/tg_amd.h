@@ -111,6 +111,9 @@ typedef struct {
   int64_t regen_timed;  /* k_regen launches timed (while tg_set_timing is on) */
   int64_t regen_launches; /* k_regen launches (deferred MT regenerations, tg_regenerate) */
   double classify_ms;   /* of kernel_ms, k_classify */
+  int64_t regens_quiet; /* of regens, the generations regenerated inside k_run by its waves without
+                           a chunk: the stale halves of envs whose option could not run in the step
+                           that listed them (compact mode; the rest are k_regen's, or the lanes') */
 } tg_stats;
 
 /* Create N envs on `device`: env i is `random.seed(seed_base + global_offset + i);

@@ -53,6 +53,11 @@ def main():
               % (idle.sum(),
                  *np.percentile((ist - t00) / 100.0, [10, 50, 90]),
                  *np.percentile((ien - t00) / 100.0, [10, 50, 90, 100])))
+        drain = idle & (buf[:, 10] > 0)  # k_run's quiet drain: the idle waves that regenerated halves
+        if drain.any():
+            den = (buf[drain, 5].astype(np.int64) - t00) / 100.0
+            print("quiet drain: %d waves, %d halves; ended by 50%% %.1f 90%% %.1f 100%% %.1f us"
+                  % (drain.sum(), int(buf[drain, 10].sum()), *np.percentile(den, [50, 90, 100])))
     act = allw & ~idle
     b = buf[act].astype(np.float64)
     mx = (buf[act, 3] & 0xFFFFFFFF).astype(np.float64)
