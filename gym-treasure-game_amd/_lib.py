@@ -33,6 +33,7 @@ TG_ACT_TANH = 1
 TG_MLP_SAMPLE = 0
 TG_MLP_GREEDY = 1
 TG_E_INVAL = -1
+TG_E_NOMEM = -3
 TG_E_STATE = -5
 OBS_DIM = 9
 NUM_ACTIONS = 9
@@ -43,7 +44,7 @@ EXPORTS = ("tg_create", "tg_destroy", "tg_num_envs", "tg_reset", "tg_step", "tg_
            "tg_available_mask",
            "tg_observe", "tg_policy_actions", "tg_episodes", "tg_errors", "tg_set_mode", "tg_set_timing", "tg_regenerate",
            "tg_set_episode_capacity", "tg_predicate_table",
-           "tg_get_stats", "tg_stats_reset", "tg_kernel_info", "tg_mt_layout", "tg_probe_dispatch", "tg_read_state", "tg_write_state", "tg_render_init", "tg_frame_shape",
+           "tg_get_stats", "tg_stats_reset", "tg_kernel_info", "tg_mt_layout", "tg_probe_dispatch", "tg_live_resources", "tg_read_state", "tg_write_state", "tg_render_init", "tg_frame_shape",
            "tg_render", "tg_frame_shape_scaled", "tg_render_scaled", "tg_policy_mlp_load", "tg_policy_mlp",
            "tg_rollout_mlp", "tg_last_error", "tg_version")
 
@@ -121,6 +122,7 @@ def load():
         "tg_set_groups": (i32, [P, i32, i32]),
         "tg_mt_layout": (i32, [ctypes.POINTER(ctypes.c_int32)] * 3),
         "tg_probe_dispatch": (i32, [i32, i32, P]),
+        "tg_live_resources": (i64, []),
         "tg_kernel_info": (i32, [P, i32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
                                  ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
         "tg_read_state": (i32, [P, P, P, P, P, P, P, P]),

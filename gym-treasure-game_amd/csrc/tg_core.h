@@ -100,6 +100,36 @@ struct Env {
   uint32_t mti;          // MT state word: position ([0, MT_WORDS), even) | MT_STALE (see Rng)
 };
 
+// ---- the st4 codec ---------------------------------------------------------------------------
+// An env's 16-B state word in HBM (Soa::st4, the worklist copies, tg_read_state / tg_write_state):
+//   x = px | py << 16 (i16 pair), y = the flag word, z = kx, ky, gx, gy (i8 x 4), w = mti.
+// The only code that knows the layout; st4_flags reads the flag word alone (one dword load).
+TG_HD void unpack_st4(const uint4 s, Env& e) {
+  e.px = (int)(int16_t)(s.x & 0xFFFFu);
+  e.py = (int)(int16_t)(s.x >> 16);
+  e.f = s.y;
+  e.kx = (int)(int8_t)(s.z & 0xFF);
+  e.ky = (int)(int8_t)((s.z >> 8) & 0xFF);
+  e.gx = (int)(int8_t)((s.z >> 16) & 0xFF);
+  e.gy = (int)(int8_t)(s.z >> 24);
+  e.mti = s.w;
+}
+TG_HD void unpack(const uint4 s, const double2 a, Env& e) {
+  unpack_st4(s, e);
+  e.ang0 = a.x;
+  e.ang1 = a.y;
+}
+TG_HD uint4 pack(const Env& e) {
+  uint4 s;
+  s.x = ((uint32_t)e.px & 0xFFFFu) | ((uint32_t)e.py << 16);
+  s.y = e.f;
+  s.z = ((uint32_t)e.kx & 0xFF) | (((uint32_t)e.ky & 0xFF) << 8) | (((uint32_t)e.gx & 0xFF) << 16) |
+        ((uint32_t)e.gy << 24);
+  s.w = e.mti;
+  return s;
+}
+TG_HD uint32_t st4_flags(const uint4& s) { return s.y; }
+
 TG_HD int floordiv(int a, int b) {  // Python // for b > 0
   int q = a / b;
   return (a % b != 0 && a < 0) ? q - 1 : q;
@@ -569,6 +599,11 @@ TG_HD uint32_t refill_after(uint32_t* mt, uint32_t state, uint8_t* mc = nullptr)
   return pos;
 }
 
+// init_genrand(19650218): the common prefix of every init_by_array (seed_mt's genrand19650218)
+inline void genrand_prefix(uint32_t gen[MT_N]) {
+  gen[0] = 19650218u;
+  for (int i = 1; i < MT_N; ++i) gen[i] = 1812433253u * (gen[i - 1] ^ (gen[i - 1] >> 30)) + (uint32_t)i;
+}
 // init_by_array([seed lo, seed hi?]) into 624 words (CPython's state before its first twist)
 TG_HD void seed_mt(uint32_t* mt, const uint32_t* genrand19650218, uint64_t seed) {
   const uint32_t key0 = (uint32_t)seed, key1 = (uint32_t)(seed >> 32);

@@ -11,7 +11,7 @@
 // IEEE f64 ops (obs divisions, uniform/gauss), built with -ffp-contract=off.
 //
 // HBM layout per handle (N envs):
-//   st4[N]  uint4   {pos = px | py<<16 (i16 pair), flags, objs = kx,ky,gx,gy (i8 x4), mt_pos}
+//   st4[N]  uint4   position, flags, object cells and MT state word (tg_core.h: the st4 codec)
 //   ang[N]  double2 {handle0.angle, handle1.angle}
 //   ep[N]   int2    {episode return, episode length}
 //   mt[N][624] u32  env-major MT19937 words (2,496 B per env)
@@ -41,33 +41,7 @@ static_assert(RUN_BLOCK % 64 == 0 && BLOCK % RUN_BLOCK == 0, "whole waves, whole
 // SIMDs with the go waves (0.153 vs 0.156 ms per step)
 constexpr int PRIO_SLOW = 3;
 
-// ------------------------------------------------------------------------------------------
-// SoA pack / unpack
-// ------------------------------------------------------------------------------------------
-__device__ __forceinline__ void unpack_st4(const uint4 s, Env& e) {
-  e.px = (int)(int16_t)(s.x & 0xFFFFu);
-  e.py = (int)(int16_t)(s.x >> 16);
-  e.f = s.y;
-  e.kx = (int)(int8_t)(s.z & 0xFF);
-  e.ky = (int)(int8_t)((s.z >> 8) & 0xFF);
-  e.gx = (int)(int8_t)((s.z >> 16) & 0xFF);
-  e.gy = (int)(int8_t)(s.z >> 24);
-  e.mti = s.w;
-}
-__device__ __forceinline__ void unpack(const uint4 s, const double2 a, Env& e) {
-  unpack_st4(s, e);
-  e.ang0 = a.x;
-  e.ang1 = a.y;
-}
-__device__ __forceinline__ uint4 pack(const Env& e) {
-  uint4 s;
-  s.x = ((uint32_t)e.px & 0xFFFFu) | ((uint32_t)e.py << 16);
-  s.y = e.f;
-  s.z = ((uint32_t)e.kx & 0xFF) | (((uint32_t)e.ky & 0xFF) << 8) | (((uint32_t)e.gx & 0xFF) << 16) |
-        ((uint32_t)e.gy << 24);
-  s.w = e.mti;
-  return s;
-}
+// (the st4 words are packed and unpacked by tg_core.h's codec: pack, unpack, unpack_st4)
 
 // The level in LDS: the bordered cell grid (per-lane indexed probes) and the trigger table
 // (indexed per lane by the cascade; kernel arguments indexed per lane would be vector loads

@@ -132,7 +132,33 @@ __device__ __forceinline__ uint32_t xcc_id() {
   return x;
 }
 
+// k_flow's parameters, in its order and by type: what launch_flow (tg_amd.hip) fills by name and
+// tg_flow.hip's launcher hands to the kernel, where the compiler checks them against k_flow
+struct FlowArgs {
+  Soa S;
+  int64_t n;
+  Level L;
+  const uint32_t* grid;
+  FlowIO io;
+  EpQueue eq;
+  Flow f;
+  int64_t g0;
+  unsigned long long* stats;
+  int nstat;
+  uint32_t* err;
+  unsigned long long* ks;
+};
+
 }  // namespace
+
+namespace tg {
+// tg_flow.hip: k_flow<ar, pol> on `st`.  These types are each unit's own (unnamed namespace), so
+// the arguments cross between the units by address, with their size as the units' agreement.
+int flow_launch_args(bool ar, int pol, unsigned grid, hipStream_t st, const void* args, size_t bytes);
+inline int flow_launch(bool ar, int pol, unsigned grid, hipStream_t st, const FlowArgs& a) {
+  return flow_launch_args(ar, pol, grid, st, &a, sizeof a);
+}
+}  // namespace tg
 
 #ifdef TG_FLOW_DBG
 #include "tg_flow_diag.h"  // (diagnostic builds only: the bring-up instrumentation)

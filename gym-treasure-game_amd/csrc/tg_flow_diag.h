@@ -143,38 +143,37 @@ constexpr uint32_t FLOW_EVW = 1024;
   } while (0)
 
 // ---- host side (tg_amd.hip's launch_flow calls it; tg_flow.hip compiles it unused) ---------------
-// the diagnostic buffers behind the Flow's dbg / dbgc / dbgl pointers
-static uint32_t* g_flow_dbg_host = nullptr;  // the progress words (host-mapped)
+// the diagnostic buffers behind the Flow's dbg / dbgc / dbgl pointers (process-wide, allocated at
+// the first launch and held to the end of the process)
+struct FlowDbgWords {
+  uint32_t w[4096 * 4];  // the progress words (host-mapped)
+};
+static PinnedBuf<FlowDbgWords> g_flow_dbg;
 inline int flow_diag_setup(tg_batch* h, Flow& f) {
   auto& F = h->fl;
-  uint32_t*& dbg_host = g_flow_dbg_host;
-  static uint32_t* dbg_dev = nullptr;
-  if (!dbg_host) {
-    HIP_TRY(hipHostMalloc((void**)&dbg_host, 4096 * 4 * sizeof(uint32_t), hipHostMallocMapped));
-    HIP_TRY(hipHostGetDevicePointer((void**)&dbg_dev, dbg_host, 0));
-  }
-  memset(dbg_host, 0, 4096 * 4 * sizeof(uint32_t));
-  f.dbg = dbg_dev;
-  static uint32_t* dbgc = nullptr;
+  TG_TRY(g_flow_dbg.alloc("flow progress words"));
+  memset(g_flow_dbg.get(), 0, sizeof(FlowDbgWords));
+  f.dbg = g_flow_dbg.dev()->w;
+  static DevBuf<uint32_t> dbgc;
   const size_t ndc = (size_t)F.C * 16 + 2 * (size_t)F.P * FLOW_MAX_K * NLIST * F.jcap;
-  if (!dbgc) HIP_TRY(hipMalloc((void**)&dbgc, sizeof(uint32_t) * ndc));
-  HIP_TRY(hipMemset(dbgc, 0, sizeof(uint32_t) * ndc));
-  f.dbgc = dbgc;
+  if (!dbgc) TG_TRY(dbgc.alloc(ndc, "flow duplicate counters"));
+  HIP_TRY(hipMemset(dbgc.get(), 0, sizeof(uint32_t) * ndc));
+  f.dbgc = dbgc.get();
 #ifdef TG_FLOW_WAVELOG
   f.dbg = nullptr;  // a timing log: no host-mapped progress words, no duplicate counters
   f.dbgc = nullptr;
 #endif
-  static uint32_t* dbgl = nullptr;
+  static DevBuf<uint32_t> dbgl;
   if (getenv("TG_FLOW_LOG")) {
 #ifdef TG_FLOW_WAVELOG
-    const size_t evb = 64 + 32 * (size_t)FLOW_EVW * (size_t)h->cus * 8 * (BLOCK / 64);
-    if (!dbgl) HIP_TRY(hipMalloc((void**)&dbgl, evb));
-    HIP_TRY(hipMemset(dbgl, 0, evb));
+    const size_t evw = 16 + 8 * (size_t)FLOW_EVW * (size_t)h->cus * 8 * (BLOCK / 64);
+    if (!dbgl) TG_TRY(dbgl.alloc(evw, "flow event log"));
+    HIP_TRY(hipMemset(dbgl.get(), 0, sizeof(uint32_t) * evw));
 #else
-    if (!dbgl) HIP_TRY(hipMalloc((void**)&dbgl, 64 + 32 * (size_t)FLOW_EVCAP));
-    HIP_TRY(hipMemset(dbgl, 0, 64));
+    if (!dbgl) TG_TRY(dbgl.alloc(16 + 8 * (size_t)FLOW_EVCAP, "flow event log"));
+    HIP_TRY(hipMemset(dbgl.get(), 0, 64));
 #endif
-    f.dbgl = dbgl;
+    f.dbgl = dbgl.get();
   }
   return TG_OK;
 }
@@ -184,7 +183,7 @@ inline int flow_diag_after(tg_batch* h, const Flow& f, int k, int bpc, hipStream
   auto& F = h->fl;
   for (int ms = 0; ms < 8000 && hipStreamQuery(st) == hipErrorNotReady; ms += 10) usleep(10000);
   const bool hung = hipStreamQuery(st) == hipErrorNotReady;
-  const uint32_t* const host_words = g_flow_dbg_host;
+  const uint32_t* const host_words = g_flow_dbg.get()->w;
   int hist[64] = {0};
   for (int w = 0; w < 4096 && f.dbg; ++w) hist[host_words[w * 4] & 63]++;
   fprintf(stderr, "[flowdbg] launch %lld %s; waves by code:", (long long)F.launches, hung ? "HUNG" : "done");

@@ -639,7 +639,7 @@ __global__ __launch_bounds__(BLOCK) void k_null() {}
 __global__ __launch_bounds__(BLOCK) void k_errors(const uint4* __restrict__ st4, int64_t n,
                                                    uint32_t* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  const uint32_t f = i < n ? (st4[i].y & E_MASK) : 0u;
+  const uint32_t f = i < n ? (st4_flags(st4[i]) & E_MASK) : 0u;
   if (f) atomicOr(out, f);
 }
 

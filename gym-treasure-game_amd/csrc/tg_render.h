@@ -85,7 +85,9 @@ TG_HD uint32_t make_layer(const RenderArgs& A, int i, const uint4 st, const doub
                           Layer& l, bool& live) {
   uint32_t err = 0;
   l.handle = 0;
-  const uint32_t f = st.y;
+  Env e;
+  unpack_st4(st, e);
+  const uint32_t f = e.f;
   int cx = 0, cy = 0;
   live = true;
   if (i < 3) {  // doors (DR/:244-248)
@@ -95,8 +97,7 @@ TG_HD uint32_t make_layer(const RenderArgs& A, int i, const uint4 st, const doub
     cx = A.handle_cx[i - 3], cy = A.handle_cy[i - 3];
     l.spr = D_HANDLE_BASE;
   } else if (i == 5 || i == 7) {  // key, gold (DR/:249-252)
-    const uint32_t z = st.z >> (i == 5 ? 0 : 16);
-    cx = (int)(int8_t)(z & 0xFF), cy = (int)(int8_t)((z >> 8) & 0xFF);
+    cx = i == 5 ? e.kx : e.gx, cy = i == 5 ? e.ky : e.gy;
     l.spr = i == 5 ? D_KEY : D_GOLD;
     live = cx >= 0;
   } else if (i == 6) {  // bolt (DR/:253-256)
@@ -106,8 +107,8 @@ TG_HD uint32_t make_layer(const RenderArgs& A, int i, const uint4 st, const doub
   if (i < 8) {
     l.ox = cx * RS, l.oy = cy * RS;
   } else {  // the hero at (playerx - xscale / 2, playery), mirrored facing left (DR/:157-161)
-    l.ox = (int)(int16_t)(st.x & 0xFFFFu) - RS / 2;
-    l.oy = (int)(int16_t)(st.x >> 16);
+    l.ox = e.px - RS / 2;
+    l.oy = e.py;
     l.spr = (f & F_FACING) ? D_HERO : D_HERO_FLIP;
   }
   l.x0 = l.ox, l.x1 = l.ox + RS, l.y0 = l.oy, l.y1 = l.oy + RS;
@@ -353,6 +354,16 @@ inline uint64_t knob_table(int r) {
   uint64_t t = 0;
   for (int d = 0; d <= 2 * r; ++d) t |= (uint64_t)(hw[d] + 1) << (4 * d);
   return t;
+}
+
+// the level's part of a RenderArgs: the screen's size, the knob table, the fixed objects' cells
+inline void render_level(const Level& L, RenderArgs& A) {
+  A.W = L.W, A.H = L.H;
+  A.Wpx = L.W * RS, A.Hpx = L.H * RS, A.CH = A.Wpx * 3 / 16;  // W * 144 bytes per row: whole chunks
+  A.knob = knob_table(KNOB_R);
+  for (int k = 0; k < 3; ++k) A.door_cx[k] = L.door_cx[k], A.door_cy[k] = L.door_cy[k];
+  for (int k = 0; k < 2; ++k) A.handle_cx[k] = L.handle_cx[k], A.handle_cy[k] = L.handle_cy[k];
+  A.bolt_cx = L.bolt_cx, A.bolt_cy = L.bolt_cy;
 }
 
 // Sprites (TG_SPR_COUNT RGBA8 images of sw x sh) -> 48x48 ARGB (convert_alpha + scale).

@@ -42,29 +42,17 @@ namespace tg {
 constexpr int RBLOCK = 256;  // 4 waves (1,024 threads lost 1.5-9 ms)
 
 struct RenderState {
-  int Wpx = 0, Hpx = 0, CH = 0;  // pixels, 16-B chunks per row
-  uint4* bg = nullptr;           // static layer, RGB bytes [Hpx][Wpx*3]
-  uint4* tiles = nullptr;        // static layer + each cell-aligned sprite, per cell
-  uint32_t* spr = nullptr;       // [D_COUNT][48*48] ARGB
-  uint64_t knob = 0;             // knob half widths + 1, 4 bits per row dy = -4..4
+  DevBuf<uint4> bg;              // static layer, RGB bytes [Hpx][Wpx*3]
+  DevBuf<uint4> tiles;           // static layer + each cell-aligned sprite, per cell
+  DevBuf<uint32_t> spr;          // [D_COUNT][48*48] ARGB
   // tg_render_scaled: the host's static layer and sprites (pooled on a scale's first call)
   // and the per-scale device tables, by scale_index
   std::vector<uint32_t> bg32, dyn;
-  uint32_t* bg_small[NSCALE] = {};
-  uint32_t* tiles_small[NSCALE] = {};
+  DevBuf<uint32_t> bg_small[NSCALE];
+  DevBuf<uint32_t> tiles_small[NSCALE];
 };
 
-void render_free(RenderState* rs) {
-  if (!rs) return;
-  void* bufs[] = {rs->bg, rs->tiles, rs->spr};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
-  for (int i = 0; i < NSCALE; ++i) {
-    if (rs->bg_small[i]) (void)hipFree(rs->bg_small[i]);
-    if (rs->tiles_small[i]) (void)hipFree(rs->tiles_small[i]);
-  }
-  delete rs;
-}
+void render_free(RenderState* rs) { delete rs; }
 
 namespace {
 
@@ -275,6 +263,24 @@ __global__ __launch_bounds__(RBLOCK) void k_render_scaled(ScaledArgs P,
 
 using namespace tg;
 
+// the kernels' view of the renderer's tables and the level's object cells
+static RenderArgs render_args(const tg_batch* h) {
+  const RenderState& rs = *h->rs;
+  RenderArgs A;
+  render_level(h->L, A);
+  A.bg = rs.bg.get(), A.tiles = rs.tiles.get(), A.spr = rs.spr.get(), A.err = h->err.get();
+  return A;
+}
+// `who`'s envs [first, first + count) of the handle into `out`
+static int check_frames(const tg_batch* h, const char* who, int64_t first, int64_t count,
+                        const uint8_t* out) {
+  if (first < 0 || count < 0 || first + count > h->n || (count && !out))
+    return fail(TG_E_INVAL, "%s: envs [%lld, %lld) outside [0, %lld)", who, (long long)first,
+                (long long)(first + count), (long long)h->n);
+  if (((uintptr_t)out & 15u) != 0) return fail(TG_E_INVAL, "%s: the output must be 16-B aligned", who);
+  return TG_OK;
+}
+
 extern "C" {
 
 int tg_render_init(tg_batch* h, const uint8_t* sprites, int32_t sw, int32_t sh) {
@@ -299,24 +305,13 @@ int tg_render_init(tg_batch* h, const uint8_t* sprites, int32_t sw, int32_t sh) 
   const std::vector<uint8_t> rgb = rgb_bytes(bg32);
   const std::vector<uint32_t> dyn = dynamic_sprites(sc);
   const std::vector<uint8_t> tiles = rgb_bytes(cell_tiles(bg32, W, H, dyn));
-  RenderState* rs = new RenderState();
+  std::unique_ptr<RenderState, RenderDelete> rs(new RenderState());
   rs->bg32 = bg32, rs->dyn = dyn;  // kept for tg_render_scaled's pooling
-  rs->Wpx = Wpx, rs->Hpx = Hpx, rs->CH = Wpx * 3 / 16;  // W * 144 bytes per row: whole chunks
-  rs->knob = knob_table(KNOB_R);
-  auto undo = [&](int code) {
-    render_free(rs);
-    return code;
-  };
-  if (hipMalloc((void**)&rs->bg, rgb.size()) != hipSuccess ||
-      hipMalloc((void**)&rs->tiles, tiles.size()) != hipSuccess ||
-      hipMalloc((void**)&rs->spr, dyn.size() * 4) != hipSuccess)
-    return undo(fail(TG_E_NOMEM, "tg_render_init: device allocation failed"));
-  if (hipMemcpy(rs->bg, rgb.data(), rgb.size(), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(rs->tiles, tiles.data(), tiles.size(), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(rs->spr, dyn.data(), dyn.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-    return undo(fail(TG_E_HIP, "tg_render_init: upload failed"));
-  render_free(h->rs);
-  h->rs = rs;
+  // (whole 16-B chunks: a row is W * 144 bytes)
+  TG_TRY(rs->bg.upload(rgb.data(), rgb.size() / 16, "the renderer's static layer"));
+  TG_TRY(rs->tiles.upload(tiles.data(), tiles.size() / 16, "the renderer's cell tiles"));
+  TG_TRY(rs->spr.upload(dyn.data(), dyn.size(), "the renderer's sprites"));
+  h->rs = std::move(rs);  // (in place of an earlier one)
   return TG_OK;
 }
 
@@ -330,19 +325,9 @@ int tg_frame_shape(const tg_batch* h, int32_t* height, int32_t* width) {
 int tg_render(tg_batch* h, int64_t first, int64_t count, uint8_t* rgb, void* stream) {
   BIND(h);
   if (!h->rs) return fail(TG_E_STATE, "tg_render: call tg_render_init first");
-  if (first < 0 || count < 0 || first + count > h->n || (count && !rgb))
-    return fail(TG_E_INVAL, "tg_render: envs [%lld, %lld) outside [0, %lld)", (long long)first,
-                (long long)(first + count), (long long)h->n);
-  if (((uintptr_t)rgb & 15u) != 0) return fail(TG_E_INVAL, "tg_render: rgb must be 16-B aligned");
+  TG_TRY(check_frames(h, "tg_render", first, count, rgb));
   if (!count) return TG_OK;
-  const RenderState* rs = h->rs;
-  RenderArgs A;
-  A.bg = rs->bg, A.tiles = rs->tiles, A.spr = rs->spr, A.err = h->err;
-  A.Wpx = rs->Wpx, A.Hpx = rs->Hpx, A.CH = rs->CH, A.H = h->L.H, A.W = h->L.W;
-  A.knob = rs->knob;
-  for (int k = 0; k < 3; ++k) A.door_cx[k] = h->L.door_cx[k], A.door_cy[k] = h->L.door_cy[k];
-  for (int k = 0; k < 2; ++k) A.handle_cx[k] = h->L.handle_cx[k], A.handle_cy[k] = h->L.handle_cy[k];
-  A.bolt_cx = h->L.bolt_cx, A.bolt_cy = h->L.bolt_cy;
+  const RenderArgs A = render_args(h);
   const int64_t blocks = (count + RG - 1) / RG * h->L.H;
   if (blocks > 0x7FFFFFFF) return fail(TG_E_INVAL, "tg_render: too many envs in one call");
   hipLaunchKernelGGL(k_render, dim3((unsigned)blocks), dim3(RBLOCK), 0, (hipStream_t)stream, A,
@@ -360,7 +345,7 @@ static int scaled_dims(const tg_batch* h, int32_t scale, int* si) {
 
 int tg_frame_shape_scaled(const tg_batch* h, int32_t scale, int32_t* height, int32_t* width) {
   int si;
-  if (int rc = scaled_dims(h, scale, &si)) return rc;
+  TG_TRY(scaled_dims(h, scale, &si));
   if (height) *height = h->L.H * RS / scale;
   if (width) *width = h->L.W * RS / scale;
   return TG_OK;
@@ -371,44 +356,25 @@ int tg_render_scaled(tg_batch* h, int64_t first, int64_t count, int32_t scale, i
   BIND(h);
   if (!h->rs) return fail(TG_E_STATE, "tg_render_scaled: call tg_render_init first");
   int si;
-  if (int rc = scaled_dims(h, scale, &si)) return rc;
+  TG_TRY(scaled_dims(h, scale, &si));
   if (channels != TG_FRAME_RGB && channels != TG_FRAME_GRAY)
     return fail(TG_E_INVAL, "tg_render_scaled: channels must be TG_FRAME_RGB or TG_FRAME_GRAY");
-  if (first < 0 || count < 0 || first + count > h->n || (count && !out))
-    return fail(TG_E_INVAL, "tg_render_scaled: envs [%lld, %lld) outside [0, %lld)",
-                (long long)first, (long long)(first + count), (long long)h->n);
-  if (((uintptr_t)out & 15u) != 0)
-    return fail(TG_E_INVAL, "tg_render_scaled: out must be 16-B aligned");
+  TG_TRY(check_frames(h, "tg_render_scaled", first, count, out));
   if (!count) return TG_OK;
-  RenderState* rs = h->rs;
+  RenderState* rs = h->rs.get();
   const int W = h->L.W, H = h->L.H;
   if (!rs->bg_small[si]) {  // this scale's first call: pool on the host, upload (synchronises)
     const std::vector<uint32_t> b = pooled_static(rs->bg32, W, H, scale);
     const std::vector<uint32_t> t = pooled_tiles(rs->bg32, W, H, rs->dyn, scale);
-    uint32_t *db = nullptr, *dt = nullptr;
-    if (hipMalloc((void**)&db, b.size() * 4) != hipSuccess ||
-        hipMalloc((void**)&dt, t.size() * 4) != hipSuccess) {
-      if (db) (void)hipFree(db);
-      return fail(TG_E_NOMEM, "tg_render_scaled: device allocation failed");
-    }
-    if (hipMemcpy(db, b.data(), b.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dt, t.data(), t.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-      (void)hipFree(db);
-      (void)hipFree(dt);
-      return fail(TG_E_HIP, "tg_render_scaled: upload failed");
-    }
-    rs->bg_small[si] = db, rs->tiles_small[si] = dt;
+    DevBuf<uint32_t> db, dt;  // installed once both are uploaded
+    TG_TRY(db.upload(b.data(), b.size(), "a scale's static layer"));
+    TG_TRY(dt.upload(t.data(), t.size(), "a scale's cell tiles"));
+    rs->bg_small[si] = std::move(db), rs->tiles_small[si] = std::move(dt);
   }
   ScaledArgs P;
-  RenderArgs& A = P.A;
-  A.bg = rs->bg, A.tiles = rs->tiles, A.spr = rs->spr, A.err = h->err;
-  A.Wpx = rs->Wpx, A.Hpx = rs->Hpx, A.CH = rs->CH, A.H = H, A.W = W;
-  A.knob = rs->knob;
-  for (int k = 0; k < 3; ++k) A.door_cx[k] = h->L.door_cx[k], A.door_cy[k] = h->L.door_cy[k];
-  for (int k = 0; k < 2; ++k) A.handle_cx[k] = h->L.handle_cx[k], A.handle_cy[k] = h->L.handle_cy[k];
-  A.bolt_cx = h->L.bolt_cx, A.bolt_cy = h->L.bolt_cy;
-  P.bg_small = rs->bg_small[si], P.tiles_small = rs->tiles_small[si];
-  P.s = scale, P.cs = RS / scale, P.w = rs->Wpx / scale, P.h = rs->Hpx / scale;
+  P.A = render_args(h);
+  P.bg_small = rs->bg_small[si].get(), P.tiles_small = rs->tiles_small[si].get();
+  P.s = scale, P.cs = RS / scale, P.w = P.A.Wpx / scale, P.h = P.A.Hpx / scale;
   P.ch = channels, P.fast = 1;  // fast: scaled_pixel's switch (host check); the kernel has none
   const int64_t group_px = (int64_t)SG * P.h * P.w;
   if (group_px > 0x7FFFFFFF - SSPAN)

@@ -289,6 +289,11 @@ int tg_mt_layout(int32_t *ring_words, int32_t *stored_words, int32_t *code_bytes
  * empty kernel of `blocks` 256-thread workgroups on `stream` (the platform's dispatch gap between
  * two dependent kernels, and an idle GPU's first dispatch).  No reference counterpart. */
 int tg_probe_dispatch(int32_t kernels, int32_t blocks, void *stream);
+/* Diagnostic: the device buffers, pinned host buffers, streams and events the library holds in
+ * this process now, over every handle (one counter, kept where they are acquired and released).
+ * It returns to its earlier value when a handle is destroyed, and when a call fails.  No
+ * reference counterpart. */
+int64_t tg_live_resources(void);
 
 /* Raw SoA state copy-out for checkpoints and tests (host buffers, synchronises; the MT
  * generations are gathered on the device and copied out in chunks of 64 Ki envs):

@@ -76,8 +76,7 @@ int hc_run(const char* dom, const char* objs, const char* inter, uint64_t seed_b
   if (!load_level(dom, objs, inter, Lv, grid, tab)) return -1;
   const Level* L = &Lv;
   uint32_t gen[MT_N];
-  gen[0] = 19650218u;
-  for (int i = 1; i < MT_N; ++i) gen[i] = 1812433253u * (gen[i - 1] ^ (gen[i - 1] >> 30)) + (uint32_t)i;
+  genrand_prefix(gen);
   const Map m{grid.data(), L->W, L->H, L->masks};
   const uint32_t* trig = &L->trig[0][0];
   const int64_t T1 = (int64_t)steps + 1;
@@ -150,8 +149,7 @@ int hc_run(const char* dom, const char* objs, const char* inter, uint64_t seed_b
 // itself if it gets there.  out = every value, in order.
 int hc_rng_stream(uint64_t seed, const int32_t* launches, int nl, int defer, double* out) {
   uint32_t gen[MT_N];
-  gen[0] = 19650218u;
-  for (int i = 1; i < MT_N; ++i) gen[i] = 1812433253u * (gen[i - 1] ^ (gen[i - 1] >> 30)) + (uint32_t)i;
+  genrand_prefix(gen);
   std::vector<uint32_t> mt(MT_WORDS);
   init_mt(mt.data(), gen, seed);
   uint32_t state = 0;
@@ -189,8 +187,7 @@ int64_t hc_check_code_top27(int64_t* slow) {
 // of all 16 generations.  Returns the mismatches.
 int64_t hc_check_mt_pair(uint64_t seed) {
   uint32_t gen[MT_N];
-  gen[0] = 19650218u;
-  for (int i = 1; i < MT_N; ++i) gen[i] = 1812433253u * (gen[i - 1] ^ (gen[i - 1] >> 30)) + (uint32_t)i;
+  genrand_prefix(gen);
   std::vector<uint32_t> mt(MT_STORE), full((size_t)(2 * MT_HALF_GENS + 1) * MT_N);
   init_mt(mt.data(), gen, seed);
   seed_mt(full.data(), gen, seed);  // generation -1, then 16 twists: the ring's generations
@@ -221,6 +218,42 @@ int64_t hc_check_code_lean(int64_t* slow) {
     bad += (c == tg::CODE_SLOW) + (tg::top27_code(a) != c);
   }
   *slow = ns;
+  return bad;
+}
+
+// The st4 codec (tg_core.h pack / unpack): round trips at the field extremes, and three words
+// computed by hand, so the format is pinned and not only self-consistent.  Returns the mismatches.
+int64_t hc_check_st4_codec(void) {
+  int64_t bad = 0;
+  const int p16[4] = {-32768, -1, 0, 32767}, c8[4] = {-128, -1, 0, 127};
+  const uint32_t w32[2] = {0u, 0xFFFFFFFFu};
+  for (int a = 0; a < 4; ++a)
+    for (int b = 0; b < 4; ++b)
+      for (int c = 0; c < 256; ++c)  // the four object cells, two bits each
+        for (int d = 0; d < 4; ++d) {
+          Env e{};
+          e.px = p16[a], e.py = p16[b];
+          e.kx = c8[c & 3], e.ky = c8[(c >> 2) & 3], e.gx = c8[(c >> 4) & 3], e.gy = c8[c >> 6];
+          e.f = w32[d & 1], e.mti = w32[d >> 1];
+          e.ang0 = 0.25 * a, e.ang1 = -0.5 * b;
+          const uint4 s = pack(e);
+          double2 an;
+          an.x = e.ang0, an.y = e.ang1;
+          Env r{};
+          unpack(s, an, r);  // (unpack_st4, then the angles)
+          bad += r.px != e.px || r.py != e.py || r.f != e.f || r.kx != e.kx || r.ky != e.ky ||
+                 r.gx != e.gx || r.gy != e.gy || r.mti != e.mti || r.ang0 != e.ang0 || r.ang1 != e.ang1;
+          bad += s.y != e.f || s.w != e.mti || st4_flags(s) != e.f;
+        }
+  Env e{};
+  e.px = -2, e.py = 3;
+  bad += pack(e).x != 0x0003FFFEu;
+  e = Env{};
+  e.kx = -1, e.ky = 2, e.gx = 3, e.gy = -4;
+  bad += pack(e).z != 0xFC0302FFu;
+  e = Env{};
+  e.f = 0x89ABCDEFu;
+  bad += pack(e).y != 0x89ABCDEFu || pack(e).x != 0u || pack(e).z != 0u || pack(e).w != 0u;
   return bad;
 }
 
@@ -272,17 +305,11 @@ int hc_render_run(const char* dom, const char* objs, const char* inter, uint64_t
   RenderArgs A;
   A.bg = reinterpret_cast<const uint4*>(bg.data());
   A.tiles = reinterpret_cast<const uint4*>(tiles.data());
-  A.W = L->W;
   A.spr = dyn.data();
   A.err = &err;
-  A.Wpx = L->W * RS, A.Hpx = L->H * RS, A.CH = A.Wpx * 3 / 16, A.H = L->H;
-  A.knob = knob_table(KNOB_R);
-  for (int k = 0; k < 3; ++k) A.door_cx[k] = L->door_cx[k], A.door_cy[k] = L->door_cy[k];
-  for (int k = 0; k < 2; ++k) A.handle_cx[k] = L->handle_cx[k], A.handle_cy[k] = L->handle_cy[k];
-  A.bolt_cx = L->bolt_cx, A.bolt_cy = L->bolt_cy;
+  render_level(*L, A);
   uint32_t gen[MT_N];
-  gen[0] = 19650218u;
-  for (int i = 1; i < MT_N; ++i) gen[i] = 1812433253u * (gen[i - 1] ^ (gen[i - 1] >> 30)) + (uint32_t)i;
+  genrand_prefix(gen);
   const Map m{grid.data(), L->W, L->H};
   const uint32_t* trig = &L->trig[0][0];
   std::vector<uint32_t> mt(MT_WORDS);
@@ -314,12 +341,7 @@ int hc_render_run(const char* dom, const char* objs, const char* inter, uint64_t
       if (autoreset && r.done) reset_env(*L, e, rng);
       e.mti = rng.finish();
     }
-    uint4 st;  // k_render reads the SoA state words
-    st.x = ((uint32_t)e.px & 0xFFFFu) | ((uint32_t)e.py << 16);
-    st.y = e.f;
-    st.z = ((uint32_t)e.kx & 0xFF) | (((uint32_t)e.ky & 0xFF) << 8) | (((uint32_t)e.gx & 0xFF) << 16) |
-           ((uint32_t)e.gy << 24);
-    st.w = e.mti;
+    const uint4 st = pack(e);  // k_render reads the SoA state words
     double2 an;
     an.x = e.ang0, an.y = e.ang1;
     uint4* out = reinterpret_cast<uint4*>(frames + (size_t)i * fb);

@@ -71,20 +71,14 @@ int hcs_render_run(const char* dom, const char* objs, const char* inter, uint64_
   RenderArgs& A = P.A;
   A.bg = reinterpret_cast<const uint4*>(bg.data());
   A.tiles = nullptr;  // the full-size tiles are not read by the scaled paths
-  A.W = L->W;
   A.spr = dyn.data();
   A.err = &err;
-  A.Wpx = L->W * RS, A.Hpx = L->H * RS, A.CH = A.Wpx * 3 / 16, A.H = L->H;
-  A.knob = knob_table(KNOB_R);
-  for (int k = 0; k < 3; ++k) A.door_cx[k] = L->door_cx[k], A.door_cy[k] = L->door_cy[k];
-  for (int k = 0; k < 2; ++k) A.handle_cx[k] = L->handle_cx[k], A.handle_cy[k] = L->handle_cy[k];
-  A.bolt_cx = L->bolt_cx, A.bolt_cy = L->bolt_cy;
+  render_level(*L, A);
   P.bg_small = bgs.data(), P.tiles_small = tls.data();
   P.s = scale, P.cs = RS / scale, P.w = A.Wpx / scale, P.h = A.Hpx / scale;
   P.ch = channels, P.fast = fast;
   uint32_t gen[MT_N];
-  gen[0] = 19650218u;
-  for (int i = 1; i < MT_N; ++i) gen[i] = 1812433253u * (gen[i - 1] ^ (gen[i - 1] >> 30)) + (uint32_t)i;
+  genrand_prefix(gen);
   const Map m{grid.data(), L->W, L->H};
   const uint32_t* trig = &L->trig[0][0];
   std::vector<uint32_t> mt(MT_WORDS);
@@ -116,12 +110,7 @@ int hcs_render_run(const char* dom, const char* objs, const char* inter, uint64_
       if (autoreset && r.done) reset_env(*L, e, rng);
       e.mti = rng.finish();
     }
-    uint4 st;  // the SoA state words the kernel reads
-    st.x = ((uint32_t)e.px & 0xFFFFu) | ((uint32_t)e.py << 16);
-    st.y = e.f;
-    st.z = ((uint32_t)e.kx & 0xFF) | (((uint32_t)e.ky & 0xFF) << 8) | (((uint32_t)e.gx & 0xFF) << 16) |
-           ((uint32_t)e.gy << 24);
-    st.w = e.mti;
+    const uint4 st = pack(e);  // the SoA state words the kernel reads
     double2 an;
     an.x = e.ang0, an.y = e.ang1;
     if (states) states[4 * i] = st.x, states[4 * i + 1] = st.y, states[4 * i + 2] = st.z, states[4 * i + 3] = 0u;

@@ -209,6 +209,18 @@ def test_odd_generation_words_equal_the_twist(hostcheck, seed):
     assert hostcheck.hc_check_mt_pair(seed) == 0
 
 
+def test_st4_codec_round_trips_and_is_pinned(hostcheck):
+    """The one st4 codec (tg_core.h pack / unpack / unpack_st4, which the kernels, tg_read_state /
+    tg_write_state, the renderer and the host checks all use): Env values at the field extremes
+    (px, py in {-32768, -1, 0, 32767}; the four object cells in {-128, -1, 0, 127}; f and mti in
+    {0, 0xFFFFFFFF}) survive pack -> unpack, and three hand-computed words hold literally:
+    px=-2, py=3 gives x == 0x0003FFFE; kx=-1, ky=2, gx=3, gy=-4 gives z == 0xFC0302FF; f gives y
+    unchanged"""
+    hostcheck.hc_check_st4_codec.restype = ctypes.c_int64
+    hostcheck.hc_check_st4_codec.argtypes = []
+    assert hostcheck.hc_check_st4_codec() == 0
+
+
 def test_lean_draw_code_equals_top27(hostcheck):
     """top27_code / top27_slow (the wave twist's code pass, tg_twist.h: the class from a's top
     two bits plus one compare) equal code_of_top27 on every a they decide, and the slow set
