@@ -462,6 +462,24 @@ struct SrvReaper {
   }
 } g_srv_reaper;
 
+// k_serve1's dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) belongs to the kernel
+// on a device, not to a handle: it is only ever raised, to the largest size any handle's server
+// has asked for there, so a handle with a smaller table never lowers it under one whose server
+// will be relaunched with a larger.  False: the runtime refused the size.
+std::vector<size_t> g_srv_dyn_max;  // by device (g_srv_mu)
+bool srv_dyn_limit(int device, size_t dyn) {
+  std::lock_guard<std::mutex> lk(g_srv_mu);
+  if (g_srv_dyn_max.size() <= (size_t)device) g_srv_dyn_max.resize((size_t)device + 1, 0);
+  if (dyn <= g_srv_dyn_max[device]) return true;
+  if (hipFuncSetAttribute((const void*)k_serve1, hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)dyn) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  g_srv_dyn_max[device] = dyn;
+  return true;
+}
+
 // launch k_serve1 on the server's stream, after the work queued on the caller's stream
 int srv_start(tg_batch* h, hipStream_t caller) {
   One& o = h->one;
@@ -481,10 +499,7 @@ int srv_start(tg_batch* h, hipStream_t caller) {
       stage = SRV_STAGE_GOTAB;
       dyn = gb;
     }
-    if (dyn > 65536 &&
-        hipFuncSetAttribute((const void*)k_serve1, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)dyn) != hipSuccess) {
-      (void)hipGetLastError();
+    if (dyn > 65536 && !srv_dyn_limit(h->device, dyn)) {
       stage = 0u;
       dyn = 0;
     }

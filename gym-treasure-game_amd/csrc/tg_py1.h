@@ -264,12 +264,12 @@ __global__ __launch_bounds__(64) void k_serve1(Soa Sg, Level Lg, const uint32_t*
     const unsigned long long t_seen = __builtin_amdgcn_s_memrealtime();
     int ticks = 0;
     const uint32_t word = __builtin_amdgcn_readfirstlane(cg.x);
-    const uint32_t kind = word & 15u;
+    const uint32_t kind = srv_kind(word);  // (tg_srv_word.h, beside the host's encoder)
     if (kind == SRV_QUIT) {
       served = s;
       break;
     }
-    const int action = (int)((word >> 4) & 31u) - 16;
+    const int action = srv_action(word);  // an action out of range arrives as one (-16)
     const uint32_t tstep = __builtin_amdgcn_readfirstlane(cg.y);
     if (kind == SRV_MASK) {  // available_mask (TG/:83-89), as k_mask
       if (lane == 0) {
@@ -306,9 +306,9 @@ __global__ __launch_bounds__(64) void k_serve1(Soa Sg, Level Lg, const uint32_t*
       ticks = step_env<false, false, POL_IMMEDIATE, true>(S, 1, L, lv.trig, m, (lds_u8*)win, lane, io,
                                                           q, g0, stats, err_or).ticks;
     } else {
-      const bool warm = (word >> 9) & 1u;
-      const int has_gauss = (int)((word >> 10) & 1u);
-      const uint32_t q0 = word >> 11;
+      const bool warm = srv_warm(word);
+      const int has_gauss = (int)srv_has_gauss(word);
+      const uint32_t q0 = srv_q0(word);
       double gauss_next = 0.0;
       if (kind == SRV_RESET_PY) {
         const uint32_t* gp = reinterpret_cast<const uint32_t*>(&box->gauss_bits);

@@ -149,7 +149,11 @@ int tg_step(tg_batch *h, const int32_t *actions, double *obs, int32_t *reward, u
  * synchronisation per call.  The server is launched by the first such call (after the work
  * queued on `stream`), stopped by any other call on the handle, and leaves by itself after
  * TG_SERVE_IDLE_US (default 500) microseconds without a command.  With serving off: one launch
- * on `stream` and one synchronisation of it. */
+ * on `stream` and one synchronisation of it.
+ * An action outside [-9, 8] (any int32; the reference raises IndexError) is not an error of the
+ * call, served or not, here and in tg_step1_py / tg_step1_pywords: it returns TG_OK with
+ * valid = 0, reward = 0 and the env's current obs, runs no option and takes no draw (a caller's
+ * stream state comes back as given), and sets TG_ERR_ACTION in tg_errors, as tg_step does. */
 int tg_step1(tg_batch *h, int32_t action, double *obs, int32_t *reward, uint8_t *valid,
              uint8_t *done, void *stream);
 

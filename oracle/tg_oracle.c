@@ -182,7 +182,7 @@ enum { A_NOP = 0, A_UP, A_DOWN, A_LEFT, A_RIGHT, A_JUMP, A_INTERACT };
 #define JUMP_REWARD (-5)
 #define STEP_REWARD (-1)
 
-#define MAXW 64
+#define MAXW 128 /* (the product's widest level is 120 cells, tg_level.h) */
 #define MAXH 64
 #define MAXOBJ 32
 #define MAXTRIG 16

@@ -13,6 +13,7 @@
 #include "../../gym-treasure-game_amd/csrc/tg_core.h"
 #include "../../gym-treasure-game_amd/csrc/tg_level.h"
 #include "../../gym-treasure-game_amd/csrc/tg_render.h"
+#include "../../gym-treasure-game_amd/csrc/tg_srv_word.h"
 
 using namespace tg;
 
@@ -256,6 +257,21 @@ int64_t hc_check_st4_codec(void) {
   bad += pack(e).y != 0x89ABCDEFu || pack(e).x != 0u || pack(e).z != 0u || pack(e).w != 0u;
   return bad;
 }
+
+// The N = 1 server's command word (tg_srv_word.h): the host's encoder, and k_serve1's decoders
+// into out[5] = kind, action, warm, has_gauss, q0.  hc_option_index: what the device's step makes
+// of a decoded action (tg_core.h option_index; -1: out of range, TG_ERR_ACTION).
+uint32_t hc_srv_word(uint32_t kind, int32_t action, int warm, int has_gauss, uint32_t q0) {
+  return srv_word(kind, action, warm != 0, has_gauss != 0, q0);
+}
+void hc_srv_fields(uint32_t word, int32_t* out) {
+  out[0] = (int32_t)srv_kind(word);
+  out[1] = srv_action(word);
+  out[2] = srv_warm(word);
+  out[3] = srv_has_gauss(word);
+  out[4] = (int32_t)srv_q0(word);
+}
+int hc_option_index(int action) { return option_index(action); }
 
 // the six collision predicates at a pixel position / door state (same bit order as the
 // oracle's tgo_predicates)

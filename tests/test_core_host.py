@@ -221,6 +221,41 @@ def test_st4_codec_round_trips_and_is_pinned(hostcheck):
     assert hostcheck.hc_check_st4_codec() == 0
 
 
+def test_server_command_word_round_trips(hostcheck):
+    """The N = 1 server's command word (csrc/tg_srv_word.h: srv_word on the host, the srv_*
+    decoders in k_serve1): every field survives for every kind, every action of [-9, 8] with both
+    flags and q0 at 0, 1, 623 and 624; and an action outside that range decodes to one that is
+    out of range again (option_index == -1: the device raises TG_ERR_ACTION and runs nothing),
+    never to a valid one (before: (action + 16) & 31, so 25 ran as -7 and 40 as 8)."""
+    L = hostcheck
+    L.hc_srv_word.restype = ctypes.c_uint32
+    L.hc_srv_word.argtypes = [ctypes.c_uint32, ctypes.c_int32, ctypes.c_int, ctypes.c_int,
+                              ctypes.c_uint32]
+    L.hc_srv_fields.restype = None
+    L.hc_srv_fields.argtypes = [ctypes.c_uint32, ctypes.POINTER(ctypes.c_int32)]
+    L.hc_option_index.restype = ctypes.c_int
+    L.hc_option_index.argtypes = [ctypes.c_int]
+    out = (ctypes.c_int32 * 5)()
+
+    def fields(*a):
+        L.hc_srv_fields(L.hc_srv_word(*a), out)
+        return tuple(out)
+
+    for kind in range(1, 7):
+        for a in range(-9, 9):
+            for warm in (0, 1):
+                for hg in (0, 1):
+                    for q0 in (0, 1, 623, 624):
+                        assert fields(kind, a, warm, hg, q0) == (kind, a, warm, hg, q0)
+            assert L.hc_option_index(a) == a % 9
+    bad = [-10, 9, 23, 25, 40, -41, 2**31 - 1, -2**31, 15, 16, -16, -17, 8 + 32, -9 - 32]
+    for a in bad:
+        for kind in (1, 2):
+            got = fields(kind, a, 1, 1, 624)
+            assert (got[0],) + got[2:] == (kind, 1, 1, 624), a
+            assert not -9 <= got[1] <= 8 and L.hc_option_index(got[1]) == -1, (a, got[1])
+
+
 def test_lean_draw_code_equals_top27(hostcheck):
     """top27_code / top27_slow (the wave twist's code pass, tg_twist.h: the class from a's top
     two bits plus one compare) equal code_of_top27 on every a they decide, and the slow set
