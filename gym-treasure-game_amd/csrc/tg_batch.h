@@ -14,7 +14,7 @@
 #include <vector>
 
 #include "../../include/tg_amd.h"
-#include "tg_core.h"
+#include "tg_state.h"
 #include "tg_srv_word.h"
 
 namespace tg {
@@ -45,8 +45,8 @@ struct Soa {
   uint4* st4;
   double2* ang;
   int2* ep;
-  uint32_t* mt;   // [N][MT_STORE]: the ring's even generations (tg_core.h)
-  uint8_t* mc;    // [N][MT_CODES]: the draw codes of the ring's generations (tg_core.h draw_code)
+  uint32_t* mt;   // [N][MT_STORE]: the ring's even generations (tg_mt.h)
+  uint8_t* mc;    // [N][MT_CODES]: the draw codes of the ring's generations (tg_mt.h draw_code)
 };
 
 // tg_step1's result row (one env)
@@ -309,9 +309,9 @@ struct tg_batch {
   tg::Level L{};
   tg::DevBuf<uint32_t> grid;  // bordered cell grid, padded to whole words
   tg::DevBuf<uint32_t> genrand;
-  tg::DevBuf<uint32_t> gotab;  // GoTable (tg_core.h go_lookup): W * H * 32 entries
-  tg::DevBuf<uint32_t> masks;  // the level bitmasks (tg_core.h Map::mk), or none
-  tg::DevBuf<double> obs_q;    // get_state's quotient table (tg_core.h Level::obs_q)
+  tg::DevBuf<uint32_t> gotab;  // GoTable (tg_rules.h go_lookup): W * H * 32 entries
+  tg::DevBuf<uint32_t> masks;  // the level bitmasks (tg_map.h Map::mk), or none
+  tg::DevBuf<double> obs_q;    // get_state's quotient table (tg_state.h Level::obs_q)
   std::string domain;          // domain.txt text (the renderer's cell sprites)
   // the envs: the kernels' view S and the arrays it points to
   tg::Soa S{};

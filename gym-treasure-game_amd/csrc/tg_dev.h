@@ -142,32 +142,20 @@ static_assert(WIN_WAVE_BYTES >= WAVE_SCRATCH, "wave_refill reuses the window as 
 static_assert(WIN_DRAWS - WIN_UNIT + 1 >= (int)MAX_TICK_DRAWS, "a refilled window holds a tick's draws");
 
 // LDS-DMA of one WIN_UNIT-byte unit per active lane into LDS [m0 + lane * WIN_UNIT]; M0 is
-// saved/restored.  SC1: the load bypasses this CU's L1 (k_flow, whose codes another CU of the
-// XCD may have rewritten in the same launch: tg_flow.h)
-template <bool SC1 = false>
-__device__ __forceinline__ void glds_unit(uint32_t m0, const void* gptr) {
-  uint32_t save;
-  if constexpr (SC1)
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %1\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %2, off sc1\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(save)
-        : "s"(__builtin_amdgcn_readfirstlane(m0)), "v"(gptr)
-        : "memory");
-  else
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %1\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %2, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(save)
-        : "s"(__builtin_amdgcn_readfirstlane(m0)), "v"(gptr)
-        : "memory");
-}
+// saved/restored.  MOD: the load's cache modifiers ("": none)
+#define TG_GLDS_UNIT(MOD, m0, gptr)                                       \
+  do {                                                                    \
+    uint32_t save_;                                                       \
+    asm volatile(                                                         \
+        "s_mov_b32 %0, m0\n\t"                                            \
+        "s_mov_b32 m0, %1\n\t"                                            \
+        "s_nop 0\n\t"                                                     \
+        "global_load_lds_dwordx4 %2, off" MOD "\n\t"                      \
+        "s_mov_b32 m0, %0"                                                \
+        : "=&s"(save_)                                                    \
+        : "s"(__builtin_amdgcn_readfirstlane(m0)), "v"(gptr)              \
+        : "memory");                                                      \
+  } while (0)
 
 // the rare second crossing (RngCodes::fill), out of line so that the draw sites stay small, its
 // generation loops out of line too: a callee's registers add to its caller's allocation (k_run
@@ -182,97 +170,70 @@ __device__ __noinline__ void regen_half(uint32_t* mt, uint8_t* mc, uint32_t h) {
   twist_half(mt, h, mc, false, GenCalls());
   asm volatile("s_waitcnt vmcnt(0)\n\tbuffer_inv sc0" ::: "memory");
 }
-// k_flow's form: the half's source words may have been written by another CU of the XCD in the
-// same launch (the env's previous item ran there), so this CU's L1 is invalidated first; the
-// stores go through the L1 (write-through) to the XCD's L2, where the env's next item, on
-// whichever CU of the XCD, reads them with L1-bypassing loads (tg_flow.h) once this wave's
-// stores are complete.  No L2 writeback: nothing crosses XCDs (an agent-scope release's
-// buffer_wbl2 here wrote back the XCD's whole L2 on every per-lane regeneration).
-__device__ __noinline__ void regen_half_flow(uint32_t* mt, uint8_t* mc, uint32_t h) {
-  asm volatile("buffer_inv sc1\n\ts_waitcnt vmcnt(0)" ::: "memory");
-  twist_half(mt, h, mc, false, GenCalls());
-  asm volatile("s_waitcnt vmcnt(0)\n\tbuffer_inv sc1\n\ts_waitcnt vmcnt(0)" ::: "memory");
-}
 
-// a stored MT word read past this CU's L1 (an agent-scope relaxed load: global_load sc1), for
-// k_flow, where another CU of the XCD may have rewritten it in the same launch (tg_flow.h)
-struct Sc1Ld {
-  __device__ uint32_t operator()(const uint32_t* p) const {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+// How a kernel reaches the env state and the MT ring in HBM: the memory model that load_env,
+// store_env, RngCodesT and the step's epilogue (finish_env, run_epilogue, run_listed) are written
+// over.  This is the per-step kernels' model: whoever wrote those bytes was an earlier launch on
+// the stream or this lane itself, so stream order makes them visible and plain loads, plain stores
+// and the plain LDS-DMA do; the one wait is the window's, landed before the first result store.
+// (k_flow hands envs from wave to wave inside one launch: its model is tg_flow.h's, beside the
+// coherence rules it implements.)
+struct LaunchMem {
+  // one env's state words at index `at` of their arrays.  (Each word is copied whole before it is
+  // assigned: the 16-B and 8-B vector loads.  Assigned straight from the array, or returned by
+  // value from a function, the compiler splits them into dword loads and k_classify, k_step and
+  // k_serve1 take 2-3 more VGPRs.)
+  static __device__ __forceinline__ void load(const uint4* st4, const double2* ang, const int2* ep,
+                                              int64_t at, uint4& s4, double2& a2, int2& e2) {
+    const uint4 s = st4[at];
+    s4 = s;
+    const double2 a = ang[at];
+    a2 = a;
+    const int2 p = ep[at];
+    e2 = p;
   }
-};
-__device__ __noinline__ WordPair mt_pair_ool_sc1(const uint32_t* mt, uint32_t p) {
-  WordPair r;
-  mt_pair(mt, p, r.w0, r.w1, Sc1Ld());
-  return r;
-}
-// k_flow's env state, handed from wave to wave inside one launch (tg_flow.h "Coherence"): loads
-// past this CU's L1 (16 B at byte offset off of base: buffer_load_dwordx4 ... sc1), and
-// write-through (sc1) stores, which leave the CU for the XCD's L2 before the storing wave's
-// `s_waitcnt vmcnt(0)` lets it publish them (plain stores were seen stale by the consumer: the
-// bring-up runs read unwritten list entries)
-__device__ __forceinline__ uint4 ld16_sc1(const void* base, uint32_t off) {
-  const __amdgpu_buffer_rsrc_t r =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, -1, 0x00020000);
-  const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 16 /* sc1 */);
-  return make_uint4(v[0], v[1], v[2], v[3]);
-}
-__device__ __forceinline__ double2 ld_ang_sc1(const double2* a, int64_t i) {
-  const uint4 v = ld16_sc1(a, (uint32_t)i * 16u);
-  return make_double2(__hiloint2double((int)v.y, (int)v.x), __hiloint2double((int)v.w, (int)v.z));
-}
-__device__ __forceinline__ int2 ld_ep_sc1(const int2* p, int64_t i) {
-  const uint64_t v = __hip_atomic_load(reinterpret_cast<const uint64_t*>(p + i), __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);
-  return make_int2((int)(uint32_t)v, (int)(uint32_t)(v >> 32));
-}
-__device__ __forceinline__ void st16_sc1(void* base, uint32_t off, uint4 v) {
-  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(base, (short)0, -1, 0x00020000);
-  typedef unsigned v4u __attribute__((ext_vector_type(4)));
-  const v4u w = {v.x, v.y, v.z, v.w};
-  __builtin_amdgcn_raw_buffer_store_b128(w, r, off, 0, 16 /* sc1 */);
-}
-__device__ __forceinline__ void st_ep_sc1(int2* p, int64_t i, int2 v) {
-  __hip_atomic_store(reinterpret_cast<uint64_t*>(p + i),
-                     (uint64_t)(uint32_t)v.x | ((uint64_t)(uint32_t)v.y << 32), __ATOMIC_RELAXED,
-                     __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint4 d2u4(double2 d) {
-  const uint64_t a = (uint64_t)__double_as_longlong(d.x), b = (uint64_t)__double_as_longlong(d.y);
-  return make_uint4((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32));
-}
-// one env's state words: from the arrays st4 / ang / ep at index at (the handle's, or k_run's
-// worklist-ordered copies), and back to the handle's (ep_too false: the episode words are
-// unchanged, a reward-None step: no store).  FLOW: k_flow's forms above
-template <bool FLOW>
-__device__ __forceinline__ void load_env(const uint4* st4, const double2* ang, const int2* ep, int64_t at,
-                                         uint4& s4, double2& a2, int2& e2) {
-  s4 = FLOW ? ld16_sc1(st4, (uint32_t)at * 16u) : st4[at];
-  a2 = FLOW ? ld_ang_sc1(ang, at) : ang[at];
-  e2 = FLOW ? ld_ep_sc1(ep, at) : ep[at];
-}
-template <bool FLOW>
-__device__ __forceinline__ void load_env(const uint4* st4, const double2* ang, const int2* ep, int64_t at,
-                                         Env& e, int2& e2) {
-  uint4 s4;
-  double2 a2;
-  load_env<FLOW>(st4, ang, ep, at, s4, a2, e2);
-  unpack(s4, a2, e);
-}
-template <bool FLOW>
-__device__ __forceinline__ void store_env(const Soa& S, int64_t i, const Env& e, int2 ep, bool ep_too = true) {
-  if constexpr (FLOW) {
-    st16_sc1(S.st4, (uint32_t)i * 16u, pack(e));
-    st16_sc1(S.ang, (uint32_t)i * 16u, d2u4(make_double2(e.ang0, e.ang1)));
-    st_ep_sc1(S.ep, i, ep);
-  } else {
+  // ep_too false: the episode words are unchanged, a reward-None step: no store.  (ep by value,
+  // as store_env takes it: profiles/headers/isa_compare.log)
+  static __device__ __forceinline__ void store(const Soa& S, int64_t i, const Env& e, int2 ep,
+                                               bool ep_too) {
     S.st4[i] = pack(e);
     S.ang[i] = make_double2(e.ang0, e.ang1);
     if (ep_too) S.ep[i] = ep;
   }
+  // the code window's DMA, a stale half's per-lane regeneration, a draw's two words
+  static __device__ __forceinline__ void glds(uint32_t m0, const void* gptr) { TG_GLDS_UNIT("", m0, gptr); }
+  static __device__ __forceinline__ void regen(uint32_t* mt, uint8_t* mc, uint32_t h) { regen_half(mt, mc, h); }
+  static __device__ __forceinline__ WordPair pair(const uint32_t* mt, uint32_t p) { return mt_pair_ool(mt, p); }
+  // The step's epilogue lands the window before its first result store: stores count in vmcnt
+  // too, so a wait placed after them is a wait for their acknowledgement.  Then nothing is in
+  // flight at RngCodesT::finish, and no wait stands behind those stores; a caller that did not
+  // (k_reset) still lands its window there.
+  template <class R>
+  static __device__ __forceinline__ void before_rows(R& rng) { rng.drain(); }
+  template <class R>
+  static __device__ __forceinline__ void at_finish(R& rng) { rng.drain(); }
+};
+// one env's state words: from the arrays st4 / ang / ep at index at (the handle's, or k_run's
+// worklist-ordered copies), and back to the handle's.  Mem: the kernel's memory model
+template <class Mem>
+__device__ __forceinline__ void load_env(const uint4* st4, const double2* ang, const int2* ep, int64_t at,
+                                         uint4& s4, double2& a2, int2& e2) {
+  Mem::load(st4, ang, ep, at, s4, a2, e2);
+}
+template <class Mem>
+__device__ __forceinline__ void load_env(const uint4* st4, const double2* ang, const int2* ep, int64_t at,
+                                         Env& e, int2& e2) {
+  uint4 s4;
+  double2 a2;
+  load_env<Mem>(st4, ang, ep, at, s4, a2, e2);
+  unpack(s4, a2, e);
+}
+template <class Mem>
+__device__ __forceinline__ void store_env(const Soa& S, int64_t i, const Env& e, int2 ep, bool ep_too = true) {
+  Mem::store(S, i, e, ep, ep_too);
 }
 
-template <bool FLOW = false>  // FLOW: k_flow's L1-bypassing loads (tg_flow.h)
+template <class Mem = LaunchMem>
 struct RngCodesT {
   static constexpr uint32_t NONE = 0xFFFFFFFFu;
   uint32_t* mt;      // this env's MT_STORE stored words (HBM)
@@ -307,8 +268,7 @@ struct RngCodesT {
     if (e / (MT_HALF / 2) != d / (MT_HALF / 2)) {
       const uint32_t left_half = mt_half(pos), entered_half = (uint32_t)MT_HALF - left_half;
       if (stale == entered_half) {
-        if (FLOW) regen_half_flow(mt, mc, entered_half);
-        else regen_half(mt, mc, entered_half);
+        Mem::regen(mt, mc, entered_half);
         ++regens;
       }
       stale = left_half;
@@ -327,8 +287,7 @@ struct RngCodesT {
       const uint32_t w0 = pos, w1 = pos + 2u * ((uint32_t)WIN_DRAWS - d % (uint32_t)WIN_UNIT);
       if ((w0 < stale + (uint32_t)MT_HALF && stale < w1) ||
           (w1 > (uint32_t)MT_WORDS && stale < w1 - (uint32_t)MT_WORDS)) {
-        if (FLOW) regen_half_flow(mt, mc, stale);
-        else regen_half(mt, mc, stale);
+        Mem::regen(mt, mc, stale);
         ++regens;
         stale = NONE;
       }
@@ -336,7 +295,7 @@ struct RngCodesT {
 #pragma unroll
     for (int j = 0; j < WIN_SLOTS; ++j) {
       const uint32_t c = c0 + j < CODE_UNITS ? c0 + j : c0 + j - CODE_UNITS;
-      glds_unit<FLOW>(m0 + j * WIN_SLOT_BYTES, mc + c * (uint32_t)WIN_UNIT);
+      Mem::glds(m0 + j * WIN_SLOT_BYTES, mc + c * (uint32_t)WIN_UNIT);
     }
     rd = d % (uint32_t)WIN_UNIT;
     left = (uint32_t)WIN_DRAWS - rd;
@@ -410,7 +369,7 @@ struct RngCodesT {
     uint32_t p = (pos >> 1) + n;
     p = 2u * (p >= (uint32_t)MT_CODES ? p - (uint32_t)MT_CODES : p);
     (void)code();
-    const WordPair w = FLOW ? mt_pair_ool_sc1(mt, p) : mt_pair_ool(mt, p);
+    const WordPair w = Mem::pair(mt, p);
     return mt_double(w.w0, w.w1);
   }
   __device__ __forceinline__ double uniform(double a, double b) { return a + (b - a) * random(); }
@@ -422,22 +381,16 @@ struct RngCodesT {
   // drain the DMAs (the window is reused as scratch); returns the state word to store: the
   // entry's stale half, still stale, keeps its bits (listed or not); a half left in this launch
   // is stale and not listed yet; none, if the lane regenerated the stale half itself.
-  // The per-step kernels call drain() before their first result store, so nothing is in flight
-  // here and no wait stands behind those stores; a caller that did not (k_reset) still lands
-  // its window.  k_flow keeps the unconditional wait it had.
+  // (Mem::at_finish: the model's wait for the window)
   __device__ __forceinline__ uint32_t finish() {
-    if constexpr (FLOW) {
-      if (primed) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    } else {
-      drain();
-    }
+    Mem::at_finish(*this);
     sync();
     primed = loaded = false;
     return pos | (stale == NONE ? 0u : entered ? MT_STALE : tag);
   }
 };
 
-using RngCodes = RngCodesT<false>;
+using RngCodes = RngCodesT<>;
 
 __device__ __forceinline__ uint64_t readlane64(uint64_t v, int lane) {
   const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)v, lane);
@@ -514,30 +467,7 @@ struct StepIO {
                                    // an episode's length is tstep + 1 - its start step (S.ep.y)
 };
 
-__device__ __forceinline__ uint64_t sm64(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-// the synthetic policies (tg_policy_actions): a[t, g] = h(a0, g, t) % 9, or the k-th set bit
-// of available_mask with k = h % popcount (masked-uniform; h % 9 when nothing can run)
-__device__ __forceinline__ int policy_action(const Level& L, const Map& m, const Env& e,
-                                             int policy, uint64_t a0, int64_t g, int64_t t) {
-  const uint64_t h = sm64(sm64(a0 ^ sm64((uint64_t)g)) ^ (uint64_t)t);
-  int a = (int)(h % 9ull);
-  if (policy == TG_POLICY_MASKED) {
-    const uint32_t mk = available_mask(L, m, e);
-    const int c = __popc(mk);
-    if (c) {
-      uint32_t k = (uint32_t)(h % (uint64_t)c);
-      uint32_t mm = mk;
-      while (k--) mm &= mm - 1u;
-      a = __ffs(mm) - 1;
-    }
-  }
-  return a;
-}
+// (the synthetic policies' action, POL >= 0: tg_rules.h policy_action)
 struct EpQueue {
   tg_episode* __restrict__ eps;
   int32_t* count;
@@ -684,13 +614,13 @@ __device__ __forceinline__ void store_obs_wave(double* __restrict__ out, int64_t
 
 // ---- one env's step after its option (step_env; k_run's and k_flow's run_listed) ---------------
 // The env's rows, its MT state word (a half left here: MT_STALE, listed by the next
-// classification), the lane's draws and own regenerations, its error bits.  The per-step kernels
-// land the window before their first result store; k_flow keeps the wait in RngCodesT::finish
-template <bool AUTORESET, bool FINAL, bool VALID, bool FLOW>
-__device__ __forceinline__ void finish_env(const Level& L, Env& e, RngCodesT<FLOW>& rng, int64_t i,
+// classification), the lane's draws and own regenerations, its error bits.  (Mem::before_rows:
+// the model's wait for the window, if it takes it ahead of the result stores)
+template <bool AUTORESET, bool FINAL, bool VALID, class Mem>
+__device__ __forceinline__ void finish_env(const Level& L, Env& e, RngCodesT<Mem>& rng, int64_t i,
                                            const StepResult& r, int2& ep, const StepIO& io,
                                            uint32_t* err_or, uint32_t& draws, int& lregen) {
-  if constexpr (!FLOW) rng.drain();
+  Mem::before_rows(rng);
   finish_step<AUTORESET, FINAL, VALID>(level_div(L), e, rng, i, r, ep, io);
   e.mti = rng.finish();
   draws = rng.draws;
@@ -700,14 +630,14 @@ __device__ __forceinline__ void finish_env(const Level& L, Env& e, RngCodesT<FLO
 // The wave's epilogue: completed episodes, the envs' state back, the launch counters (slot sl).
 // ep_in: the episode words as loaded (stored only if changed), or null (always stored).  steps /
 // valid / wregens: counted where the caller steps whole envs.  Every lane of the wave reaches it.
-template <bool AUTORESET, bool FLOW, bool ONE = false>  // ONE: only lane 0 live (k_serve1)
+template <bool AUTORESET, class Mem, bool ONE = false>  // ONE: only lane 0 live (k_serve1)
 __device__ __forceinline__ void run_epilogue(const Soa& S, bool live, int64_t i, int64_t g, const Env& e,
                                              int2& ep, const int2* ep_in, const StepResult& r,
                                              uint32_t draws, int lregen, uint32_t tstep, const EpQueue& q,
                                              unsigned long long* __restrict__ stats, int64_t sl, int steps = 0,
                                              int valid = 0, int wregens = 0) {
   if (AUTORESET) record_episodes(live && r.done, g, ep, tstep, q, stats, sl);
-  if (live) store_env<FLOW>(S, i, e, ep, !ep_in || ep.x != ep_in->x || ep.y != ep_in->y);
+  if (live) store_env<Mem>(S, i, e, ep, !ep_in || ep.x != ep_in->x || ep.y != ep_in->y);
   __builtin_amdgcn_s_setprio(0);
   const int eps = AUTORESET ? (live && r.done) : 0;
   if constexpr (ONE)
@@ -738,7 +668,7 @@ __device__ __forceinline__ StepResult step_env(const Soa& S, int64_t n, const Le
   e.mti = 0u;
   int2 ep = make_int2(0, 0), ep_in = ep;
   if (live) {
-    load_env<false>(S.st4, S.ang, S.ep, i, e, ep);
+    load_env<LaunchMem>(S.st4, S.ang, S.ep, i, e, ep);
     ep_in = ep;
     RngCodes rng(S.mt + i * MT_STORE, S.mc + i * MT_CODES, e.mti, wscr);
     int act;
@@ -758,7 +688,7 @@ __device__ __forceinline__ StepResult step_env(const Soa& S, int64_t n, const Le
   wave_refill(need, S.mt + (live ? i : 0) * MT_STORE, S.mc + (live ? i : 0) * MT_CODES, e.mti,
               (lds_u32*)wscr);
   e.mti &= ~(MT_STALE | MT_LISTED);
-  run_epilogue<AUTORESET, false, ONE>(S, live, i, g0 + i, e, ep, &ep_in, r, draws, lregen, io.tstep, q,
+  run_epilogue<AUTORESET, LaunchMem, ONE>(S, live, i, g0 + i, e, ep, &ep_in, r, draws, lregen, io.tstep, q,
                                       stats, blockIdx.x, live ? 1 : 0, r.ran, __popcll(need));
   return r;
 }
@@ -936,12 +866,12 @@ __device__ __forceinline__ LaneGroup lane_groups(int bk) {
 }
 // A listed env's step from its loaded state through its rows (valid: the deciding pass's): option
 // k, wave-uniform (one specialised loop; L_RESET: none, reward None).  hook: RunStamp or NoRunHook
-template <bool AUTORESET, bool FINAL, bool FLOW, class Hook>
+template <bool AUTORESET, bool FINAL, class Mem, class Hook>
 __device__ __forceinline__ void run_listed(const Level& L, const uint32_t* trig, const Map& m, const Soa& S,
                                            int64_t i, int k, Env& e, int2& ep, lds_u8* wscr,
                                            const StepIO& io, uint32_t* err_or, StepResult& r,
                                            uint32_t& draws, int& lregen, Hook& hook) {
-  RngCodesT<FLOW> rng(S.mt + i * MT_STORE, S.mc + i * MT_CODES, e.mti, wscr);
+  RngCodesT<Mem> rng(S.mt + i * MT_STORE, S.mc + i * MT_CODES, e.mti, wscr);
   rng.prime();  // issue the code loads now; the first draw comes after the policy setup
   hook.env_loaded();
   if (k != O_GO_LEFT && k != O_GO_RIGHT && k != O_INTERACT) __builtin_amdgcn_s_setprio(PRIO_SLOW);

@@ -158,7 +158,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   double2 a2 = make_double2(0.0, 0.0);
   int2 ep = make_int2(0, 0);
   if (live) {
-    load_env<false>(S.st4, S.ang, S.ep, i, s4, a2, ep);
+    load_env<LaunchMem>(S.st4, S.ang, S.ep, i, s4, a2, ep);
     if constexpr (POL < 0) act = io.actions[i];
   }
   if (threadIdx.x < NLIST) bcnt[threadIdx.x] = 0;
@@ -394,12 +394,12 @@ __global__ __launch_bounds__(RUN_BLOCK) void k_run(Soa S, int64_t n, Level L,
   if (live) {
     const int64_t at = (int64_t)seg * w.shard_cap + idx;
     i = w.lists[at];
-    load_env<false>(w.wst4, w.wang, w.wep, at, e, ep);
-    run_listed<AUTORESET, FINAL, false>(L, lv.trig, lv.m, S, i, k, e, ep, wscr, io, err_or, r, draws,
+    load_env<LaunchMem>(w.wst4, w.wang, w.wep, at, e, ep);
+    run_listed<AUTORESET, FINAL, LaunchMem>(L, lv.trig, lv.m, S, i, k, e, ep, wscr, io, err_or, r, draws,
                                         lregen, stamp);
   }
   // (k_run's grid has BLOCK / RUN_BLOCK workgroups per stats slot)
-  run_epilogue<AUTORESET, false>(S, live, i, g0 + i, e, ep, nullptr, r, draws, lregen, io.tstep, q, stats,
+  run_epilogue<AUTORESET, LaunchMem>(S, live, i, g0 + i, e, ep, nullptr, r, draws, lregen, io.tstep, q, stats,
                                  (int64_t)blockIdx.x / (BLOCK / RUN_BLOCK));
   kst_end(ks, kt0);
   stamp.wave_end(live, k, r.ticks, base >> 6);

@@ -10,7 +10,7 @@
 #include <string>
 #include <vector>
 
-#include "tg_core.h"
+#include "tg_rules.h"
 
 namespace tg {
 
@@ -120,7 +120,7 @@ inline int parse_level(const char* dom, const char* objs, const char* inter, Lev
   if (PW * PH > MAX_CELLS || L.W > 120 || L.H > 120)
     return level_err(err, "level: %dx%d (+%d-cell border) exceeds the %d-cell LDS grid", L.W,
                      L.H, PAD, MAX_CELLS);
-  // bordered grid of cell bits (tg_core.h B_*): the border is WALL, like the reference's
+  // bordered grid of cell bits (tg_state.h B_*): the border is WALL, like the reference's
   // out-of-bounds probes (IM/:218-225)
   grid.assign((size_t)PW * PH, (uint8_t)B_WALL);
   bool found = false;
@@ -210,7 +210,7 @@ inline int parse_level(const char* dom, const char* objs, const char* inter, Lev
   return 0;
 }
 
-// The GoTable (tg_core.h go_lookup) of a parsed level, W * H * 32 entries, evaluated with the
+// The GoTable (tg_rules.h go_lookup) of a parsed level, W * H * 32 entries, evaluated with the
 // direct go_target / can_run code at a player standing in the middle of each cell: the key and
 // the gold at home, or off the row (a position go_lookup never answers from the table).
 inline std::vector<uint32_t> build_gotab(const Level& Lin, const std::vector<uint8_t>& grid) {
@@ -243,7 +243,7 @@ inline std::vector<uint32_t> build_gotab(const Level& Lin, const std::vector<uin
   return tab;
 }
 
-// get_state's quotient table (tg_core.h Level::obs_q): pixel coordinates Q_MIN .. (W + 2) * 48
+// get_state's quotient table (tg_state.h Level::obs_q): pixel coordinates Q_MIN .. (W + 2) * 48
 // over W * 48 and Q_MIN .. (H + 2) * 48 over H * 48 (every player and object coordinate the
 // level can produce, with margin; outside it observe divides), each the IEEE double quotient
 // (the host's division: correctly rounded, as the device's).  Sets L.qx_n / L.qy_n.
@@ -257,7 +257,7 @@ inline std::vector<double> build_obs_q(Level& L) {
   return q;
 }
 
-// The level bitmasks (tg_core.h Map::mk) of a parsed level's bordered grid, or empty when a
+// The level bitmasks (tg_map.h Map::mk) of a parsed level's bordered grid, or empty when a
 // bordered side exceeds MK_DIM cells.
 inline std::vector<uint32_t> build_masks(const Level& L, const std::vector<uint8_t>& grid) {
   const int PW = L.W + 2 * PAD, PH = L.H + 2 * PAD;

@@ -1,6 +1,6 @@
 // tg_policy_mlp.h — the learned actor's arithmetic (tg_policy_mlp / tg_rollout_mlp of
 // include/tg_amd.h), one env at a time.  Shared by k_policy_mlp (tg_kernels.h) and by
-// the host-only check build (tests/native_policy, plain g++): needs <math.h> only.
+// the host-only check build (tests/native_policy, plain g++): needs <math.h> and tg_hash.h only.
 //
 // Everything is f32 and every multiply-add is an explicit fmaf in a fixed order (the build has
 // -ffp-contract=off), so logits and value do not depend on batch size, sharding or tiling and are
@@ -18,9 +18,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#ifndef TG_HD
-#define TG_HD inline
-#endif
+#include "tg_hash.h"  // sm64, and TG_HD where the unit has not defined it (plain g++: inline)
 
 namespace tg {
 
@@ -96,15 +94,9 @@ TG_HD uint32_t mlp_allowed(int masked, uint32_t avail) {
   return (masked && a) ? a : 0x1FFu;
 }
 
-TG_HD uint64_t mlp_sm64(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
 // u in [0, 1) of (action seed, GLOBAL env index, step): the top 24 bits of policy_action's hash
 TG_HD float mlp_uniform(uint64_t a0, int64_t g, int64_t t) {
-  const uint64_t h = mlp_sm64(mlp_sm64(a0 ^ mlp_sm64((uint64_t)g)) ^ (uint64_t)t);
+  const uint64_t h = sm64(sm64(a0 ^ sm64((uint64_t)g)) ^ (uint64_t)t);
   return (float)(h >> 40) * 0x1p-24f;
 }
 

@@ -21,7 +21,7 @@
 #include <vector>
 
 #include "../../include/tg_amd.h"
-#include "tg_core.h"
+#include "tg_mt.h"
 
 namespace tg {
 

@@ -1,7 +1,7 @@
 // tg_twist.h — whole-wavefront MT19937 regeneration (device only): a half of the ring
-// (MT_HALF_GENS generations, tg_core.h) twisted by the 64 lanes of one wave, the generations
+// (MT_HALF_GENS generations, tg_mt.h) twisted by the 64 lanes of one wave, the generations
 // chained in the wave's LDS scratch, every generation's 312 draw codes and the even
-// generations' 624 words stored (tg_core.h MT_STORE).
+// generations' 624 words stored (tg_mt.h MT_STORE).
 // Used by k_regen (the deferred regeneration, every 16 compact steps) and k_run's quiet drain
 // (regen_entries, tg_dev.h), k_gen_twist (tg_create,
 // tg_write_state), k_reset (tg_kernels.h) and k_step (step_env, tg_dev.h).  (The twist variants measured in isolation,
@@ -16,7 +16,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "tg_core.h"
+#include "tg_mt.h"
 
 namespace tg {
 
@@ -38,7 +38,7 @@ __device__ __forceinline__ void wave_fence() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// ---- draw codes: one tempered word per draw (tg_core.h top27_code) --------------------------
+// ---- draw codes: one tempered word per draw (tg_mt.h top27_code) --------------------------
 // A generation's 312 draw codes from its words in LDS: draw d = r * 64 + lane per round, its
 // two words one 8-B LDS read (consecutive lanes, consecutive 8 B: no bank conflict, where a
 // 4-B read of every other word conflicted 2-way), its code one byte of a coalesced 64-B store.
@@ -152,7 +152,7 @@ __device__ __forceinline__ void twist_lds(lds_u32* s, glb_u32* dst, uint8_t* dst
 }
 // `gens` generations in sequence after the one in t, ring generations g0, g0 + 1, ... of an env
 // whose stored words start at w and codes at c: each one's codes, and the words of the even
-// ones (tg_core.h mt_store_off).  With lead, one twist leads in first (t holds a stored
+// ones (tg_mt.h mt_store_off).  With lead, one twist leads in first (t holds a stored
 // generation 6; its successor, the other half's generation 7, is the chain's source: neither
 // stored nor coded).  The first twist from registers, the rest chained in the wave's LDS
 // scratch, so a half's regeneration reads one generation from HBM.  w / c wave-uniform; must

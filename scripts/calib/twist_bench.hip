@@ -28,7 +28,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "../../gym-treasure-game_amd/csrc/tg_core.h"
+#include "../../gym-treasure-game_amd/csrc/tg_mt.h"
 
 using namespace tg;
 

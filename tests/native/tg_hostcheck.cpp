@@ -3,27 +3,21 @@
 // Host-only build of the product's per-env core (gym-treasure-game_amd/csrc/tg_core.h), so
 // the exact code the gfx950 kernel runs per lane can be checked against the oracle on the
 // build machine, which has no GPU.  It replays k_step's per-lane sequence (env_step, observe,
-// optional auto-reset) one env at a time.  The product library never contains or calls this.
+// optional auto-reset) one env at a time (host_env.h: the level load and the replay, shared with
+// tests/native_scaled).  The product library never contains or calls this.
 // Built by tests/native/Makefile with hipcc --offload-host-only.
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <vector>
 
-#include "../../gym-treasure-game_amd/csrc/tg_core.h"
-#include "../../gym-treasure-game_amd/csrc/tg_level.h"
 #include "../../gym-treasure-game_amd/csrc/tg_render.h"
 #include "../../gym-treasure-game_amd/csrc/tg_srv_word.h"
+#include "host_env.h"
 
 using namespace tg;
 
 namespace {
-uint64_t sm64(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
 uint64_t rec_hash(uint64_t h, const double o[9], int32_t r, int v, int d) {
   for (int i = 0; i < 9; ++i) {
     uint64_t b;
@@ -39,31 +33,9 @@ extern "C" {
 // go_left / go_right answered from the GoTable as on the device (1, default) or directly (0)
 static int g_gotab = 1;
 void hc_set_gotab(int on) { g_gotab = on; }
-// the level bitmasks (tg_core.h Map::mk) as on the device's option loops (1, default) or not (0)
+// the level bitmasks (tg_map.h Map::mk) as on the device's option loops (1, default) or not (0)
 static int g_masks = 1;
 void hc_set_masks(int on) { g_masks = on; }
-static std::vector<uint32_t> g_mk;  // the last loaded level's masks
-static std::vector<double> g_q;     // and quotient table
-
-static bool load_level(const char* dom, const char* objs, const char* inter, Level& L,
-                       std::vector<uint8_t>& grid, std::vector<uint32_t>& tab) {
-  std::string err;
-  if (!dom) {
-    dom = kDefaultDomain;
-    objs = kDefaultObjects;
-    inter = kDefaultInteractions;
-  }
-  if (parse_level(dom, objs, inter, L, grid, err) != 0) return false;
-  if (g_gotab) {
-    tab = build_gotab(L, grid);
-    L.gotab = tab.data();
-  }
-  g_mk = g_masks ? build_masks(L, grid) : std::vector<uint32_t>();
-  L.masks = g_mk.empty() ? nullptr : g_mk.data();
-  g_q = build_obs_q(L);  // observe's quotient table, as on the device
-  L.obs_q = g_q.data();
-  return true;
-}
 
 // Level texts as tg_create takes them (NULL = built-in default).
 // obs/final_obs [n][steps+1][9], reward/valid/done [n][steps+1], hash/draws/ticks [n]
@@ -71,33 +43,15 @@ int hc_run(const char* dom, const char* objs, const char* inter, uint64_t seed_b
            int64_t n, int steps, uint64_t a0, int policy, int autoreset, double* obs,
            int32_t* reward, uint8_t* valid, uint8_t* done, double* final_obs, uint64_t* hash,
            int64_t* draws, int64_t* ticks) {
-  Level Lv;
-  std::vector<uint8_t> grid;
-  std::vector<uint32_t> tab;
-  if (!load_level(dom, objs, inter, Lv, grid, tab)) return -1;
-  const Level* L = &Lv;
-  uint32_t gen[MT_N];
-  genrand_prefix(gen);
-  const Map m{grid.data(), L->W, L->H, L->masks};
-  const uint32_t* trig = &L->trig[0][0];
+  HostLevel hl;
+  if (!hl.load(dom, objs, inter, g_gotab, g_masks)) return -1;
+  HostReplay env(hl, true);
   const int64_t T1 = (int64_t)steps + 1;
-  std::vector<uint32_t> mt(MT_WORDS);
   for (int64_t i = 0; i < n; ++i) {
     const uint64_t g = (uint64_t)(g0 + i);
-    init_mt(mt.data(), gen, seed_base + g);  // k_create + k_gen_twist
-    Env e{};
-    int64_t ndraws = 0;
-    {  // construct + reset, each a separate launch on the device (k_reset)
-      Rng rng(mt.data(), 0u);
-      reset_env(*L, e, rng);
-      e.mti = refill_after(mt.data(), rng.finish());  // k_reset refills at once
-      Rng rng2(mt.data(), e.mti);
-      reset_env(*L, e, rng2);
-      e.mti = refill_after(mt.data(), rng2.finish());
-      ndraws += rng.draws + rng2.draws;
-    }
+    env.start(seed_base + g);
     double o[9], fo[9];
-    observe(*L, e, o);
+    observe(hl.L, env.e, o);
     uint64_t h = rec_hash(g, o, 0, 0, 0);
     int64_t nt = 0;
     if (obs) memcpy(&obs[i * T1 * 9], o, sizeof o);
@@ -106,29 +60,9 @@ int hc_run(const char* dom, const char* objs, const char* inter, uint64_t seed_b
     if (valid) valid[i * T1] = 0;
     if (done) done[i * T1] = 0;
     for (int t = 0; t < steps; ++t) {
-      const uint64_t hh = sm64(sm64(a0 ^ sm64(g)) ^ (uint64_t)t);
-      int a = (int)(hh % 9ull);
-      if (policy == 1) {
-        const uint32_t mk = available_mask(*L, m, e);
-        const int c = __builtin_popcount(mk);
-        if (c) {
-          uint32_t k = (uint32_t)(hh % (uint64_t)c), mm = mk;
-          while (k--) mm &= mm - 1u;
-          a = __builtin_ctz(mm);
-        }
-      }
-      e.mti = refill_after(mt.data(), e.mti);  // the classify pass: last step's stale half
-      Rng rng(mt.data(), e.mti);  // per step, as each launch
-      const StepResult r = env_step(*L, trig, m, e, a, rng);
+      const StepResult r = env.step(a0, policy, autoreset != 0, (int64_t)g, t, fo);
       nt += r.ticks;
-      observe(*L, e, fo);
-      memcpy(o, fo, sizeof o);
-      if (autoreset && r.done) {
-        reset_env(*L, e, rng);
-        observe(*L, e, o);
-      }
-      e.mti = rng.finish();  // may carry MT_STALE into the next step
-      ndraws += rng.draws;
+      observe(hl.L, env.e, o);  // fo, or the reset env's
       h = rec_hash(h, fo, r.reward, r.ran, r.done);
       const int64_t j = i * T1 + t + 1;
       if (obs) memcpy(&obs[j * 9], o, sizeof o);
@@ -138,7 +72,7 @@ int hc_run(const char* dom, const char* objs, const char* inter, uint64_t seed_b
       if (done) done[j] = (uint8_t)r.done;
     }
     if (hash) hash[i] = h;
-    if (draws) draws[i] = ndraws;  // includes the 8 construct + reset draws
+    if (draws) draws[i] = env.draws;  // includes the 8 construct + reset draws
     if (ticks) ticks[i] = nt;
   }
   return 0;
@@ -276,11 +210,9 @@ int hc_option_index(int action) { return option_index(action); }
 // the six collision predicates at a pixel position / door state (same bit order as the
 // oracle's tgo_predicates)
 unsigned hc_predicates(int px, int py, unsigned door_bits) {
-  static Level L;
-  static std::vector<uint8_t> grid;
-  static std::vector<uint32_t> tab;
-  if (grid.empty() && !load_level(nullptr, nullptr, nullptr, L, grid, tab)) return ~0u;
-  const Map m{grid.data(), L.W, L.H};
+  static HostLevel hl;
+  if (hl.grid.empty() && !hl.load(nullptr, nullptr, nullptr, g_gotab, g_masks)) return ~0u;
+  const Map m = hl.map(false);
   Env e{};
   e.px = px;
   e.py = py;
@@ -304,13 +236,11 @@ void hc_predicate_table(int x0, int x1, int y0, int y1, unsigned door_bits, uint
 int hc_render_run(const char* dom, const char* objs, const char* inter, uint64_t seed_base,
                   const int64_t* envs, int64_t n, int steps, uint64_t a0, int policy,
                   int autoreset, const uint8_t* sprites, int sw, int sh, uint8_t* frames) {
-  Level Lv;
-  std::vector<uint8_t> grid;
-  std::vector<uint32_t> tab;
-  if (!load_level(dom, objs, inter, Lv, grid, tab)) return -1;
-  const Level* L = &Lv;
+  HostLevel hl;
+  if (!hl.load(dom, objs, inter, g_gotab, g_masks)) return -1;
+  const Level* L = &hl.L;
   std::vector<std::string> desc;
-  for (auto& l : lines_of(dom ? dom : kDefaultDomain)) desc.push_back(strip(l));
+  for (auto& l : lines_of(hl.dom)) desc.push_back(strip(l));
   while (!desc.empty() && desc.back().empty()) desc.pop_back();
   const std::vector<uint32_t> sc = scale_sprites(sprites, sw, sh);
   const std::vector<uint32_t> bg32 = static_layer(desc, L->W, L->H, sc);
@@ -324,39 +254,12 @@ int hc_render_run(const char* dom, const char* objs, const char* inter, uint64_t
   A.spr = dyn.data();
   A.err = &err;
   render_level(*L, A);
-  uint32_t gen[MT_N];
-  genrand_prefix(gen);
-  const Map m{grid.data(), L->W, L->H};
-  const uint32_t* trig = &L->trig[0][0];
-  std::vector<uint32_t> mt(MT_WORDS);
+  HostReplay env(hl, false);
   const size_t fb = (size_t)A.Hpx * A.Wpx * 3;
   for (int64_t i = 0; i < n; ++i) {
-    const uint64_t g = (uint64_t)envs[i];
-    init_mt(mt.data(), gen, seed_base + g);
-    Env e{};
-    for (int r = 0; r < 2; ++r) {  // construct + reset
-      Rng rng(mt.data(), e.mti);
-      reset_env(*L, e, rng);
-      e.mti = refill_after(mt.data(), rng.finish());
-    }
-    for (int t = 0; t < steps; ++t) {
-      const uint64_t hh = sm64(sm64(a0 ^ sm64(g)) ^ (uint64_t)t);
-      int a = (int)(hh % 9ull);
-      if (policy == 1) {
-        const uint32_t mk = available_mask(*L, m, e);
-        const int c = __builtin_popcount(mk);
-        if (c) {
-          uint32_t k = (uint32_t)(hh % (uint64_t)c), mm = mk;
-          while (k--) mm &= mm - 1u;
-          a = __builtin_ctz(mm);
-        }
-      }
-      e.mti = refill_after(mt.data(), e.mti);
-      Rng rng(mt.data(), e.mti);
-      const StepResult r = env_step(*L, trig, m, e, a, rng);
-      if (autoreset && r.done) reset_env(*L, e, rng);
-      e.mti = rng.finish();
-    }
+    env.start(seed_base + (uint64_t)envs[i]);
+    for (int t = 0; t < steps; ++t) env.step(a0, policy, autoreset != 0, envs[i], t);
+    const Env& e = env.e;
     const uint4 st = pack(e);  // k_render reads the SoA state words
     double2 an;
     an.x = e.ang0, an.y = e.ang1;

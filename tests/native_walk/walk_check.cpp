@@ -1,13 +1,13 @@
 // walk_check.cpp — TEST INFRASTRUCTURE ONLY.
 //
-// Host-only build of the plain phases' multi-draw hops (gym-treasure-game_amd/csrc/tg_core.h:
+// Host-only build of the plain phases' multi-draw hops (gym-treasure-game_amd/csrc/tg_walk.h:
 // hop_ticks, walk_hops) over a flat array of code bytes, beside walk_ticks, which specifies them,
 // over the same array.  tests/test_walk_host.py drives it.  Built by tests/native_walk/Makefile
 // with hipcc --offload-host-only; the product library never contains or calls this.
 #include <cstdint>
 #include <cstring>
 
-#include "../../gym-treasure-game_amd/csrc/tg_core.h"
+#include "../../gym-treasure-game_amd/csrc/tg_walk.h"
 
 using namespace tg;
 
@@ -115,7 +115,7 @@ int64_t wk_sweep(const uint8_t* codes, uint32_t base, int d0, int d1, int l0, in
 
 
 // One lane's rolling code window over the flat array mc[MT_CODES]: the reserve / top-up / fill
-// sequence of the form measured in DESIGN.md §3.3, written on tg_core.h's ring_* functions: from
+// sequence of the form measured in DESIGN.md §3.3, written on tg_walk.h's ring_* functions: from
 // draw index `start`, `total` draws in per-tick batches of 0..6 from a seeded generator, each
 // tick behind reserve(TICK_DRAWS), now and then reserve(MAX_TICK_DRAWS).  A DMA's slot turns
 // to garbage when it is issued and to its unit's codes when the lane waits for it, so a read
