@@ -68,6 +68,16 @@ def lib():
         L.tgo_run_render.restype = i32
         L.tgo_run_render.argtypes = [P, u64, P, i64, i32, u64, i32, i32, P, i32, i32, P, i32]
         L.tgo_choice_seq.argtypes = [u64, i32, i32, P]
+        L.tgo_env_set_state.restype = i32
+        L.tgo_env_set_state.argtypes = [P, P, ctypes.c_uint32, P, P, P, ctypes.c_uint32]
+        L.tgo_env_get_state.restype = i32
+        L.tgo_env_get_state.argtypes = [P] * 7
+        L.tgo_step_cap.restype = i32
+        L.tgo_step_cap.argtypes = [P, i32, i64, P, P, P, P]
+        L.tgo_step_states.restype = i32
+        L.tgo_step_states.argtypes = [P, i64] + [P] * 7 + [i64] + [P] * 14 + [i32]
+        L.tgo_stream_states.restype = None
+        L.tgo_stream_states.argtypes = [u64, i64, i64, P, P, i32]
         _lib = L
     return _lib
 
@@ -124,6 +134,47 @@ class OracleEnv:
         lib().tgo_reset(self._h, _p(o))
         self._obs = o
         return o
+
+    def step_cap(self, a, cap):
+        """step(a) that gives up after ``cap`` ticks: (obs, reward, done, capped)"""
+        o = np.zeros(9, np.float64)
+        r = np.zeros(1, np.int32)
+        v = np.zeros(1, np.uint8)
+        d = np.zeros(1, np.uint8)
+        rc = lib().tgo_step_cap(self._h, int(a), int(cap), _p(o), _p(r), _p(v), _p(d))
+        if rc == -1:
+            raise IndexError("list index out of range")
+        if rc < 0:
+            raise RuntimeError("oracle step failed")
+        self._obs = o
+        return o, (int(r[0]) if v[0] else None), bool(d[0]), bool(rc)
+
+    def set_state(self, state):
+        """Continue from one env's checkpoint state (the format of tg_read_state: a dict of
+        pos, flags, objs, ang and, optionally, mt and mt_pos; see tests/state_codec.py).
+        ``obs`` stays the last step's until the next step."""
+        pos = np.ascontiguousarray(state["pos"], np.int32)
+        objs = np.ascontiguousarray(state["objs"], np.int32)
+        ang = np.ascontiguousarray(state["ang"], np.float64)
+        mt = np.ascontiguousarray(state["mt"], np.uint32) if "mt" in state else None
+        assert pos.shape == (2,) and objs.shape == (4,) and ang.shape == (2,)
+        assert mt is None or mt.shape == (624,)
+        rc = lib().tgo_env_set_state(self._h, _p(pos), int(state["flags"]), _p(objs), _p(ang),
+                                     _p(mt), int(state["mt_pos"]) if mt is not None else 0)
+        if rc != 0:
+            raise ValueError("oracle: not a state of the checkpoint format")
+
+    def get_state(self):
+        """The env's state in the checkpoint format; mt_pos is CPython's index (1..624)"""
+        st = {"pos": np.zeros(2, np.int32), "objs": np.zeros(4, np.int32),
+              "ang": np.zeros(2, np.float64), "mt": np.zeros(624, np.uint32)}
+        f, p = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        rc = lib().tgo_env_get_state(self._h, _p(st["pos"]), ctypes.byref(f), _p(st["objs"]),
+                                     _p(st["ang"]), _p(st["mt"]), ctypes.byref(p))
+        if rc != 0:
+            raise ValueError("oracle: the env's state does not fit the checkpoint format")
+        st["flags"], st["mt_pos"] = np.uint32(f.value), np.uint32(p.value)
+        return st
 
     def mask(self):
         return int(lib().tgo_mask(self._h))
@@ -193,6 +244,59 @@ def run_episodes(seed_base, g0, n, steps, action_seed, policy=0, t_from=0, nthre
     if rc != 0:
         raise RuntimeError("oracle run failed")
     return int(cnt.value), int(dig.value)
+
+
+TICK_CAP = 1 << 14  # the product's limit (include/tg_amd.h TG_ERR_TICKCAP)
+
+
+def step_states(states, actions=None, cap=TICK_CAP, nthreads=0, level_dir=None, mt_out=True):
+    """One step from each given state (a batch state in the checkpoint format: pos [n, 2],
+    flags [n], objs [n, 4], ang [n, 2], mt [n, 624], mt_pos [n]) with actions [n], an option
+    giving up after ``cap`` ticks.  Returns mask (available_mask before the step), obs, reward,
+    valid, done, the state after (pos, flags, objs, ang, mt, mt_pos; CPython's index, 1..624),
+    ticks, draws and capped.  ``actions`` None: the masks only (mt is not needed then)."""
+    pos = np.ascontiguousarray(states["pos"], np.int32)
+    n = len(pos)
+    flags = np.ascontiguousarray(states["flags"], np.uint32)
+    objs = np.ascontiguousarray(states["objs"], np.int32)
+    ang = np.ascontiguousarray(states["ang"], np.float64)
+    assert pos.shape == (n, 2) and flags.shape == (n,) and objs.shape == (n, 4)
+    assert ang.shape == (n, 2)
+    out = {"mask": np.zeros(n, np.uint16)}
+    mt = mt_pos = act = None
+    if actions is not None:
+        mt = np.ascontiguousarray(states["mt"], np.uint32)
+        mt_pos = np.ascontiguousarray(states["mt_pos"], np.uint32)
+        act = np.ascontiguousarray(actions, np.int32)
+        assert mt.shape == (n, 624) and mt_pos.shape == (n,) and act.shape == (n,)
+        out.update(obs=np.zeros((n, 9), np.float64), reward=np.zeros(n, np.int32),
+                   valid=np.zeros(n, np.uint8), done=np.zeros(n, np.uint8),
+                   pos=np.zeros((n, 2), np.int32), flags=np.zeros(n, np.uint32),
+                   objs=np.zeros((n, 4), np.int32), ang=np.zeros((n, 2), np.float64),
+                   mt_pos=np.zeros(n, np.uint32), ticks=np.zeros(n, np.int64),
+                   draws=np.zeros(n, np.int64), capped=np.zeros(n, np.uint8))
+        if mt_out:
+            out["mt"] = np.zeros((n, 624), np.uint32)
+    g = out.get
+    rc = lib().tgo_step_states(level(level_dir), n, _p(pos), _p(flags), _p(objs), _p(ang), _p(mt),
+                               _p(mt_pos), _p(act), int(cap), _p(g("obs")), _p(g("reward")),
+                               _p(g("valid")), _p(g("done")), _p(out["mask"]), _p(g("pos")),
+                               _p(g("flags")), _p(g("objs")), _p(g("ang")), _p(g("mt")),
+                               _p(g("mt_pos")), _p(g("ticks")), _p(g("draws")), _p(g("capped")),
+                               nthreads)
+    if rc != 0:
+        raise RuntimeError("oracle step_states failed")
+    return out
+
+
+def stream_states(seed_base, i0, n, nthreads=0):
+    """(mt [n, 624], mt_pos [n]): getstate() of random.Random(seed_base + i), i in [i0, i0 + n),
+    advanced so that the index cycles with i % 7 through 0 (the successor form of 624), 2, 310,
+    312, 620, 622, 624"""
+    mt = np.zeros((n, 624), np.uint32)
+    pos = np.zeros(n, np.uint32)
+    lib().tgo_stream_states(seed_base, i0, n, _p(mt), _p(pos), nthreads)
+    return mt, pos
 
 
 def rng_words(seed, n):

@@ -904,15 +904,22 @@ static int policy_step(tgo_env *e, int k, optstate *s) {
     return A_NOP;
 }
 
-/* _Option.run (OP/:20-36). Returns 1 and *rew if it ran, 0 if it could not run (None). */
-static int option_run(tgo_env *e, int k, int *rew) {
+/* _Option.run (OP/:20-36). Returns 1 and *rew if it ran, 0 if it could not run (None).
+ * cap > 0: the loop gives up once it has taken `cap` ticks (*capped = 1; the reference has no
+ * limit and would go on, for ever where the option cannot finish). */
+static int option_run(tgo_env *e, int k, int *rew, int64_t cap, int *capped) {
     if (!option_can_run(e, k)) return 0;
     optstate s = {0, 0, 0};
     int tot = 0;
+    int64_t ticks = 0;
     while (!s.done) {
         int act = policy_step(e, k, &s);
         tot += prim_step(e, act);
         if (e->err) break;
+        if (cap > 0 && ++ticks >= cap) {
+            *capped = 1;
+            break;
+        }
     }
     *rew = tot;
     return 1;
@@ -941,12 +948,12 @@ tgo_env *tgo_env_new(const tgo_level *lv, uint64_t seed, double obs[9]) {
 void tgo_env_free(tgo_env *e) { free(e); }
 
 /* TreasureGame.step (TG/:91-96) */
-int tgo_step(tgo_env *e, int action, double obs[9], int32_t *reward, uint8_t *valid,
-             uint8_t *done) {
+static int step_capped(tgo_env *e, int action, int64_t cap, double obs[9], int32_t *reward,
+                       uint8_t *valid, uint8_t *done, int *capped) {
     if (action < -9 || action > 8) return -1; /* option_list[action]: IndexError */
     if (action < 0) action += 9;
     int r = 0;
-    int ran = option_run(e, action, &r);
+    int ran = option_run(e, action, &r, cap, capped);
     if (obs) get_state(e, obs);
     if (reward) *reward = ran ? r : 0;
     if (valid) *valid = (uint8_t)ran;
@@ -954,6 +961,17 @@ int tgo_step(tgo_env *e, int action, double obs[9], int32_t *reward, uint8_t *va
     get_player_cell(e, &xc, &yc);
     if (done) *done = (uint8_t)(player_got_goldcoin(e) && yc == 0);
     return e->err ? -2 : 0;
+}
+int tgo_step(tgo_env *e, int action, double obs[9], int32_t *reward, uint8_t *valid,
+             uint8_t *done) {
+    int capped = 0;
+    return step_capped(e, action, 0, obs, reward, valid, done, &capped);
+}
+int tgo_step_cap(tgo_env *e, int action, int64_t cap, double obs[9], int32_t *reward,
+                 uint8_t *valid, uint8_t *done) {
+    int capped = 0;
+    const int rc = step_capped(e, action, cap, obs, reward, valid, done, &capped);
+    return rc ? rc : capped;
 }
 
 void tgo_reset(tgo_env *e, double obs[9]) { /* TG/:78-81 */
@@ -1498,4 +1516,164 @@ int tgo_run_render(const tgo_level *lv, uint64_t seed_base, const int64_t *envs,
         free(e);
     }
     return err ? -1 : warn;
+}
+
+/* ======================================================================================
+ * State injection: the checkpoint format of include/tg_amd.h (at tg_read_state) on this env
+ * ====================================================================================== */
+#define ST_JT 0x1Fu
+#define ST_FACING 5
+#define ST_OBJ 6
+#define ST_BAGLEN 12
+#define ST_BAGITEM 15
+
+static int find_type(const tgo_env *e, int type) {
+    for (int i = 0; i < e->nobj; i++)
+        if (e->obj[i].type == type) return i;
+    return -1;
+}
+
+int tgo_env_set_state(tgo_env *e, const int32_t pos[2], uint32_t flags, const int32_t objs[4],
+                      const double ang[2], const uint32_t mt[624], uint32_t mt_pos) {
+    const int key = find_type(e, O_KEY), gold = find_type(e, O_GOLD);
+    const int nbag = (int)(flags >> ST_BAGLEN & 7u);
+    if (e->nd > 3 || e->nh > 2 || e->nb > 1 || key < 0 || gold < 0) return -1;
+    if (mt && mt_pos > MT_N) return -1;
+    if (flags >> 22 || (flags >> ST_BAGITEM & 0x7Fu) >> nbag) return -1; /* unused / error bits */
+    e->playerx = pos[0];
+    e->playery = pos[1];
+    e->jump_ticker = (int)(flags & ST_JT);
+    e->facing_right = (int)(flags >> ST_FACING & 1u);
+    for (int i = 0; i < e->nobj; i++) e->obj[i].prev = 0;
+    for (int i = 0; i < e->nd; i++) {
+        gobj *d = &e->obj[e->doors[i]];
+        d->closed = (int)(flags >> (ST_OBJ + i) & 1u);
+        door_update_map(e, d);
+    }
+    for (int i = 0; i < e->nh; i++) {
+        gobj *h = &e->obj[e->handles[i]];
+        h->up = (int)(flags >> (ST_OBJ + 3 + i) & 1u);
+        h->angle = ang[i];
+    }
+    if (e->nb) e->obj[e->bolts[0]].locked = (int)(flags >> (ST_OBJ + 5) & 1u);
+    move_to(&e->obj[key], objs[0], objs[1]);
+    move_to(&e->obj[gold], objs[2], objs[3]);
+    e->nbag = nbag;
+    for (int j = 0; j < nbag; j++) e->bag[j] = (flags >> (ST_BAGITEM + j) & 1u) ? gold : key;
+    e->err = 0;
+    if (mt) {
+        memcpy(e->rng.mt, mt, sizeof e->rng.mt);
+        e->rng.index = (int)mt_pos;
+        e->rng.has_gauss_next = 0;
+        e->rng.gauss_next = 0.0;
+    }
+    return 0;
+}
+
+int tgo_env_get_state(const tgo_env *e, int32_t pos[2], uint32_t *flags, int32_t objs[4],
+                      double ang[2], uint32_t mt[624], uint32_t *mt_pos) {
+    const int key = find_type(e, O_KEY), gold = find_type(e, O_GOLD);
+    if (e->nd > 3 || e->nh > 2 || e->nb > 1 || key < 0 || gold < 0 || e->nbag > 7 ||
+        e->rng.has_gauss_next)
+        return -1;
+    uint32_t f = (uint32_t)e->jump_ticker & ST_JT;
+    f |= (uint32_t)(e->facing_right != 0) << ST_FACING;
+    for (int i = 0; i < e->nd; i++) f |= (uint32_t)e->obj[e->doors[i]].closed << (ST_OBJ + i);
+    for (int i = 0; i < e->nh; i++) f |= (uint32_t)e->obj[e->handles[i]].up << (ST_OBJ + 3 + i);
+    if (e->nb) f |= (uint32_t)e->obj[e->bolts[0]].locked << (ST_OBJ + 5);
+    f |= (uint32_t)e->nbag << ST_BAGLEN;
+    for (int j = 0; j < e->nbag; j++) f |= (uint32_t)(e->bag[j] == gold) << (ST_BAGITEM + j);
+    if (pos) pos[0] = e->playerx, pos[1] = e->playery;
+    if (flags) *flags = f;
+    if (objs) {
+        objs[0] = e->obj[key].cx, objs[1] = e->obj[key].cy;
+        objs[2] = e->obj[gold].cx, objs[3] = e->obj[gold].cy;
+    }
+    if (ang) {
+        ang[0] = ang[1] = 0.0;
+        for (int i = 0; i < e->nh; i++) ang[i] = e->obj[e->handles[i]].angle;
+    }
+    if (mt) memcpy(mt, e->rng.mt, sizeof e->rng.mt);
+    if (mt_pos) *mt_pos = (uint32_t)e->rng.index;
+    return 0;
+}
+
+int tgo_step_states(const tgo_level *lv, int64_t n, const int32_t *pos, const uint32_t *flags,
+                    const int32_t *objs, const double *ang, const uint32_t *mt,
+                    const uint32_t *mt_pos, const int32_t *actions, int64_t cap, double *obs,
+                    int32_t *reward, uint8_t *valid, uint8_t *done, uint16_t *mask,
+                    int32_t *pos2, uint32_t *flags2, int32_t *objs2, double *ang2, uint32_t *mt2,
+                    uint32_t *mt_pos2, int64_t *ticks, int64_t *draws, uint8_t *capped,
+                    int nthreads) {
+    int err = 0;
+    static const double zero_ang[2] = {0.0, 0.0};
+    if (actions && (!mt || !mt_pos)) return -1;
+#ifdef _OPENMP
+    if (nthreads <= 0) nthreads = omp_get_max_threads();
+    if (nthreads > 16) nthreads = 16;
+#pragma omp parallel num_threads(nthreads) reduction(| : err)
+#endif
+    {
+        tgo_env *e = (tgo_env *)malloc(sizeof(tgo_env));
+        if (!e) err |= 1;
+        else env_init(e, lv, 0, NULL);
+#ifdef _OPENMP
+#pragma omp for schedule(dynamic, 64)
+#endif
+        for (int64_t i = 0; i < n; i++) {
+            if (!e) continue;
+            if (tgo_env_set_state(e, &pos[2 * i], flags[i], &objs[4 * i],
+                                  ang ? &ang[2 * i] : zero_ang, mt ? &mt[(size_t)i * MT_N] : NULL,
+                                  mt ? mt_pos[i] : 0)) {
+                err |= 1;
+                continue;
+            }
+            if (mask) mask[i] = (uint16_t)tgo_mask(e);
+            if (!actions) continue;
+            const uint64_t d0 = e->rng.draws;
+            const int64_t t0 = e->ticks_total;
+            double o[9];
+            int32_t r = 0;
+            uint8_t v = 0, d = 0;
+            int cp = 0;
+            const int rc = step_capped(e, actions[i], cap, o, &r, &v, &d, &cp);
+            if (rc) err |= 1;
+            if (obs) memcpy(&obs[9 * i], o, sizeof o);
+            if (reward) reward[i] = r;
+            if (valid) valid[i] = v;
+            if (done) done[i] = d;
+            if (ticks) ticks[i] = e->ticks_total - t0;
+            if (draws) draws[i] = (int64_t)(e->rng.draws - d0);
+            if (capped) capped[i] = (uint8_t)cp;
+            if (tgo_env_get_state(e, pos2 ? &pos2[2 * i] : NULL, flags2 ? &flags2[i] : NULL,
+                                  objs2 ? &objs2[4 * i] : NULL, ang2 ? &ang2[2 * i] : NULL,
+                                  mt2 ? &mt2[(size_t)i * MT_N] : NULL,
+                                  mt_pos2 ? &mt_pos2[i] : NULL))
+                err |= 1;
+        }
+        free(e);
+    }
+    return err ? -1 : 0;
+}
+
+void tgo_stream_states(uint64_t seed_base, int64_t i0, int64_t n, uint32_t *mt, uint32_t *mt_pos,
+                       int nthreads) {
+    static const int kDraws[7] = {312, 1, 155, 156, 310, 311, 312};
+#ifdef _OPENMP
+    if (nthreads <= 0) nthreads = omp_get_max_threads();
+    if (nthreads > 16) nthreads = 16;
+#pragma omp parallel for schedule(static) num_threads(nthreads)
+#endif
+    for (int64_t k = 0; k < n; k++) {
+        const int64_t i = i0 + k;
+        pyrand r;
+        pr_seed(&r, seed_base + (uint64_t)i);
+        for (int d = 0; d < kDraws[i % 7]; d++) pr_random(&r);
+        if (i % 7 == 0) { /* the twist CPython would do before its next word */
+            pr_u32(&r);
+            r.index = 0;
+        }
+        memcpy(&mt[(size_t)k * MT_N], r.mt, sizeof r.mt);
+        mt_pos[k] = (uint32_t)r.index;
+    }
 }

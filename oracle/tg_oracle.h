@@ -52,6 +52,45 @@ unsigned tgo_predicates(tgo_env *e, int px, int py, unsigned door_bits);
 void tgo_predicate_table(tgo_env *e, int x0, int x1, int y0, int y1, unsigned door_bits,
                          uint8_t *out);
 
+/* --- state injection (the checkpoint format of include/tg_amd.h, at tg_read_state) --------- */
+/* The env continues from the given state: pos playerx, playery; flags the format's flag word
+ * (jump_ticker, facing_right, the door / handle / bolt booleans, the bag; its unused and error
+ * bits must be 0); objs key cx, cy, gold cx, cy; ang the handle angles in objects-file order;
+ * (mt, mt_pos) random.getstate()'s words and index, 0..624 (mt NULL: the stream stays as it
+ * is).  gauss_next is cleared, the options hold no target, total_actions and the draw and
+ * tick counters go on.  The level must have at most 3 doors, 2 handles and 1 bolt, and a key
+ * and a gold coin.  Returns 0, or -1 for a state the format does not admit. */
+int tgo_env_set_state(tgo_env *e, const int32_t pos[2], uint32_t flags, const int32_t objs[4],
+                      const double ang[2], const uint32_t mt[624], uint32_t mt_pos);
+/* The inverse (any pointer may be NULL).  mt_pos is CPython's own index, 1..624: where the
+ * product reports (successor generation, 0) this reports (generation, 624).  Returns -1 for
+ * a state the format cannot hold (a bag of more than 7, a pending gauss_next). */
+int tgo_env_get_state(const tgo_env *e, int32_t pos[2], uint32_t *flags, int32_t objs[4],
+                      double ang[2], uint32_t mt[624], uint32_t *mt_pos);
+/* tgo_step with a tick limit (cap <= 0: none): an option that has taken `cap` ticks stops
+ * there, finished or not, as the product's TICK_CAP does.  Returns 1 then (the outputs and the
+ * env hold the state after those ticks), else what tgo_step returns. */
+int tgo_step_cap(tgo_env *e, int action, int64_t cap, double obs[9], int32_t *reward,
+                 uint8_t *valid, uint8_t *done);
+/* One step from each of n given states (arrays of the fields above, case-major), on at most
+ * 16 threads: mask[i] = available_mask of state i, then step(actions[i]) under the tick limit
+ * `cap`: obs [n][9], reward / valid / done [n], the state after (pos2 .. mt_pos2), the ticks
+ * and random() draws the step took, capped[i] = 1 where it hit the limit.  actions NULL: the
+ * masks only (mt may be NULL then).  Any output may be NULL.  Returns 0 or -1. */
+int tgo_step_states(const tgo_level *lv, int64_t n, const int32_t *pos, const uint32_t *flags,
+                    const int32_t *objs, const double *ang, const uint32_t *mt,
+                    const uint32_t *mt_pos, const int32_t *actions, int64_t cap, double *obs,
+                    int32_t *reward, uint8_t *valid, uint8_t *done, uint16_t *mask,
+                    int32_t *pos2, uint32_t *flags2, int32_t *objs2, double *ang2, uint32_t *mt2,
+                    uint32_t *mt_pos2, int64_t *ticks, int64_t *draws, uint8_t *capped,
+                    int nthreads);
+/* getstate() of random.Random(seed_base + i) for i in [i0, i0 + n), advanced by 312, 1, 155,
+ * 156, 310, 311, 312 calls of random() for i % 7 = 0..6: index 624, 2, 310, 312, 620, 622,
+ * 624; i % 7 == 0 is given in the successor form (the twisted generation, index 0).
+ * mt [n][624], mt_pos [n]. */
+void tgo_stream_states(uint64_t seed_base, int64_t i0, int64_t n, uint32_t *mt, uint32_t *mt_pos,
+                       int nthreads);
+
 /* --- batched driver (the CPU baseline and the parity generator) ------------------------- */
 /* Runs envs g in [g0, g0+n), env g seeded seed_base+g, for `steps` env-steps with the
  * counter-hash action stream (policy 0 = uniform over 0..8, 1 = masked-uniform).

@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <thread>
 #include <vector>
 
 #include "../../gym-treasure-game_amd/csrc/tg_render.h"
@@ -75,6 +76,82 @@ int hc_run(const char* dom, const char* objs, const char* inter, uint64_t seed_b
     if (draws) draws[i] = env.draws;  // includes the 8 construct + reset draws
     if (ticks) ticks[i] = nt;
   }
+  return 0;
+}
+
+// One step from each of n given states (the checkpoint format of tg_read_state / tg_write_state,
+// case-major arrays): the state goes through the product's own codec (pack, then unpack, as
+// tg_write_state stores it and the kernels load it) into the core's Env, with a ring built as
+// tg_write_state builds it (the given generation first, its successors after it); then
+// available_mask and one env_step(actions[i]).  Outputs as the oracle's tgo_step_states: obs
+// [n][9], reward / valid / done [n], mask [n], the state after (flags2 with the error bits;
+// (mt2, mt_pos2) as tg_read_state reports them: the generation holding the position, index
+// 0..622), ticks and draws [n].  actions null: the masks only (mt may be null).  `threads`
+// workers, each on a contiguous share of the cases.
+int hc_step_states(const char* dom, const char* objs, const char* inter, int64_t n,
+                   const int32_t* pos, const uint32_t* flags, const int32_t* cells,
+                   const double* ang, const uint32_t* mt, const uint32_t* mt_pos,
+                   const int32_t* actions, double* obs, int32_t* reward, uint8_t* valid,
+                   uint8_t* done, uint16_t* mask, int32_t* pos2, uint32_t* flags2, int32_t* cells2,
+                   double* ang2, uint32_t* mt2, uint32_t* mt_pos2, int64_t* ticks, int64_t* draws,
+                   int threads) {
+  HostLevel hl;
+  if (!hl.load(dom, objs, inter, g_gotab, g_masks)) return -1;
+  if (actions && (!mt || !mt_pos)) return -1;
+  const Level& L = hl.L;
+  const Map m = hl.map(true);
+  const uint32_t* const trig = &L.trig[0][0];
+  const auto work = [&](int64_t lo, int64_t hi) {
+    std::vector<uint32_t> ring(MT_STORE), gen(MT_N);
+    for (int64_t i = lo; i < hi; ++i) {
+      Env t{};
+      t.px = pos[2 * i], t.py = pos[2 * i + 1];
+      t.f = flags[i];
+      t.kx = cells[4 * i], t.ky = cells[4 * i + 1], t.gx = cells[4 * i + 2], t.gy = cells[4 * i + 3];
+      t.mti = mt_pos ? mt_pos[i] : 0u;
+      double2 an;
+      an.x = ang[2 * i], an.y = ang[2 * i + 1];
+      Env e{};
+      unpack(pack(t), an, e);
+      if (mask) mask[i] = (uint16_t)available_mask(L, m, e);
+      if (!actions) continue;
+      // ring generation 0 = the given words; 1 .. 15 by plain twists, the even ones stored
+      memcpy(ring.data(), mt + i * MT_N, sizeof(uint32_t) * MT_N);
+      memcpy(gen.data(), ring.data(), sizeof(uint32_t) * MT_N);
+      for (int g = 1; g < 2 * MT_HALF_GENS; ++g) {
+        twist_gen_inplace(gen.data());
+        if (!(g & 1)) memcpy(ring.data() + mt_store_off((uint32_t)g), gen.data(), sizeof(uint32_t) * MT_N);
+      }
+      Rng rng(ring.data(), e.mti);
+      const StepResult r = env_step(L, trig, m, e, actions[i], rng);
+      e.mti = rng.finish();
+      if (obs) observe(L, e, obs + 9 * i);
+      if (reward) reward[i] = r.reward;
+      if (valid) valid[i] = (uint8_t)r.ran;
+      if (done) done[i] = (uint8_t)r.done;
+      if (ticks) ticks[i] = r.ticks;
+      if (draws) draws[i] = rng.draws;
+      if (pos2) pos2[2 * i] = e.px, pos2[2 * i + 1] = e.py;
+      if (flags2) flags2[i] = e.f;
+      if (cells2) cells2[4 * i] = e.kx, cells2[4 * i + 1] = e.ky, cells2[4 * i + 2] = e.gx, cells2[4 * i + 3] = e.gy;
+      if (ang2) ang2[2 * i] = e.ang0, ang2[2 * i + 1] = e.ang1;
+      const uint32_t p = e.mti & MT_POS_MASK, g = p / (uint32_t)MT_N;
+      if (mt_pos2) mt_pos2[i] = p - g * (uint32_t)MT_N;
+      if (mt2) {  // the generation holding p: stored, or the twist of the stored one before it
+        if (g & 1u) twist_gen(ring.data() + mt_store_off(g - 1u), mt2 + i * MT_N);
+        else memcpy(mt2 + i * MT_N, ring.data() + mt_store_off(g), sizeof(uint32_t) * MT_N);
+      }
+    }
+  };
+  if (threads < 1) threads = 1;
+  if (threads > 16) threads = 16;
+  std::vector<std::thread> pool;
+  const int64_t share = (n + threads - 1) / threads;
+  for (int w = 0; w < threads; ++w) {
+    const int64_t lo = w * share, hi = lo + share < n ? lo + share : n;
+    if (lo < hi) pool.emplace_back(work, lo, hi);
+  }
+  for (auto& th : pool) th.join();
   return 0;
 }
 
