@@ -143,21 +143,16 @@ __global__ __launch_bounds__(RBLOCK) void k_render(RenderArgs A, const uint4* __
 //      SG is a multiple of 4, so a group starts on a dword whatever the frame size.  Only a
 //      short last group's tail is stored byte by byte, so nothing outside
 //      [out, out + count * frame bytes) is written.
-constexpr int SG = 4;        // envs per group
+// SG (envs per group), SSPAN (output pixels per workgroup), SQCAP and span_pixel are
+// tg_render_scaled.h's, shared with the host check's count of a span's declined boxes.
 constexpr int SPX = 4;       // pixels per thread per store
-constexpr int SSPAN = 4096;  // output pixels per workgroup
-// Queued boxes per workgroup.  Past it a thread composes its own box inline (scaled_compose:
-// the same rows, summed in the lane).  A span holds about 4096 * 48 / Wpx hero boxes plus as
-// many again per handle, so only a level narrower than about 12 cells can get there: none of
-// the shipped or test levels does, and no GPU test reaches that branch; scaled_compose itself
-// is what the host check runs for every pixel with fast = 0.
-constexpr int SQCAP = 1024;
-
-__device__ __forceinline__ void span_pixel(int p, int fp, int w, int& k, int& x, int& y) {
-  k = p / fp;
-  const int r = p - k * fp;
-  y = r / w, x = r - y * w;
-}
+// SQCAP: queued boxes per workgroup.  Past it a thread composes its own box inline
+// (scaled_compose: the same rows, summed in the lane).  A span holds about 4096 * 48 / Wpx hero
+// boxes plus as many again per handle, so only a level narrower than about 12 cells can get
+// there: none of the shipped levels does.  tests/test_gpu_render_sweep.py reaches that branch on
+// the 8-cell level tests/golden/levels/narrow at scales 1 and 2, where the host check counts
+// more than SQCAP declined boxes in a span (hcs_span_queue_max); scaled_compose
+// itself is also what the host check runs for every pixel with fast = 0.
 
 __global__ __launch_bounds__(RBLOCK) void k_render_scaled(ScaledArgs P,
                                                           const uint4* __restrict__ st4,

@@ -36,6 +36,21 @@ struct ScaledArgs {
                                 // by the general path.  k_render_scaled does not read it.
 };
 
+// k_render_scaled's division of the work (tg_render.hip, where the passes are described): the
+// frames of a group of SG envs are one run of SG * h * w output pixels, a workgroup takes a span
+// of SSPAN of them and queues up to SQCAP boxes that scaled_lookup declines.  Here so that the
+// host check counts a span's declined boxes with the kernel's own arithmetic.
+constexpr int SG = 4;        // envs per group
+constexpr int SSPAN = 4096;  // output pixels per workgroup
+constexpr int SQCAP = 1024;  // queued boxes per workgroup
+
+// pixel p of a group's run -> env k of the group and (x, y) in its frame of fp = h * w pixels
+TG_HD void span_pixel(int p, int fp, int w, int& k, int& x, int& y) {
+  k = p / fp;
+  const int r = p - k * fp;
+  y = r / w, x = r - y * w;
+}
+
 TG_HD uint32_t luma_px(uint32_t c) {
   return (77u * ((c >> 16) & 255u) + 150u * ((c >> 8) & 255u) + 29u * (c & 255u) + 128u) >> 8;
 }

@@ -76,6 +76,8 @@ def lib():
         L.tgo_step_cap.argtypes = [P, i32, i64, P, P, P, P]
         L.tgo_step_states.restype = i32
         L.tgo_step_states.argtypes = [P, i64] + [P] * 7 + [i64] + [P] * 14 + [i32]
+        L.tgo_render_states.restype = i32
+        L.tgo_render_states.argtypes = [P, i64, P, P, P, P, P, i32, i32, P, i32]
         L.tgo_stream_states.restype = None
         L.tgo_stream_states.argtypes = [u64, i64, i64, P, P, i32]
         _lib = L
@@ -349,6 +351,27 @@ def run_render(seed_base, envs, steps, action_seed, policy, autoreset, sprites, 
                               sprites.shape[1], _p(out), nthreads)
     if rc < 0:
         raise RuntimeError("oracle run_render failed")
+    return out
+
+
+def render_states(states, sprites, level_dir=None, nthreads=0):
+    """Frames of the given states (a batch state in the checkpoint format: pos [n, 2], flags [n],
+    objs [n, 4], ang [n, 2]; streams are not read): set_state, then render, per state, threaded.
+    uint8 [n, H*48, W*48, 3] (PARITY UNPINNED renderer restatement)."""
+    pos = np.ascontiguousarray(states["pos"], np.int32)
+    n = len(pos)
+    flags = np.ascontiguousarray(states["flags"], np.uint32)
+    objs = np.ascontiguousarray(states["objs"], np.int32)
+    ang = np.ascontiguousarray(states["ang"], np.float64)
+    assert pos.shape == (n, 2) and flags.shape == (n,) and objs.shape == (n, 4)
+    assert ang.shape == (n, 2)
+    sprites = np.ascontiguousarray(sprites, np.uint8)
+    h, w = _level_frame_shape(level_dir)
+    out = np.zeros((n, h, w, 3), np.uint8)
+    rc = lib().tgo_render_states(level(level_dir), n, _p(pos), _p(flags), _p(objs), _p(ang),
+                                 _p(sprites), sprites.shape[2], sprites.shape[1], _p(out), nthreads)
+    if rc < 0:
+        raise RuntimeError("oracle render_states failed")
     return out
 
 

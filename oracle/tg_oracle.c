@@ -1656,6 +1656,38 @@ int tgo_step_states(const tgo_level *lv, int64_t n, const int32_t *pos, const ui
     return err ? -1 : 0;
 }
 
+int tgo_render_states(const tgo_level *lv, int64_t n, const int32_t *pos, const uint32_t *flags,
+                      const int32_t *objs, const double *ang, const uint8_t *sprites_rgba, int sw,
+                      int sh, uint8_t *frames, int nthreads) {
+    int err = 0, warn = 0;
+    const size_t fb = (size_t)lv->W * XSCALE * lv->H * YSCALE * 3;
+#ifdef _OPENMP
+    if (nthreads <= 0) nthreads = omp_get_max_threads();
+    if (nthreads > 16) nthreads = 16;
+#pragma omp parallel num_threads(nthreads) reduction(| : err, warn)
+#endif
+    {
+        tgo_env *e = (tgo_env *)malloc(sizeof(tgo_env));
+        if (!e) err |= 1;
+        else env_init(e, lv, 0, NULL);
+#ifdef _OPENMP
+#pragma omp for schedule(dynamic, 1)
+#endif
+        for (int64_t i = 0; i < n; i++) {
+            if (!e) continue;
+            if (tgo_env_set_state(e, &pos[2 * i], flags[i], &objs[4 * i], &ang[2 * i], NULL, 0)) {
+                err |= 1;
+                continue;
+            }
+            const int rc = tgo_render(e, sprites_rgba, sw, sh, frames + (size_t)i * fb);
+            if (rc < 0) err |= 1;
+            if (rc > 0) warn |= 1;
+        }
+        free(e);
+    }
+    return err ? -1 : warn;
+}
+
 void tgo_stream_states(uint64_t seed_base, int64_t i0, int64_t n, uint32_t *mt, uint32_t *mt_pos,
                        int nthreads) {
     static const int kDraws[7] = {312, 1, 155, 156, 310, 311, 312};

@@ -119,6 +119,12 @@ int tgo_render(const tgo_env *e, const uint8_t *sprites_rgba, int sw, int sh, ui
 int tgo_run_render(const tgo_level *lv, uint64_t seed_base, const int64_t *envs, int64_t n,
                    int steps, uint64_t action_seed, int policy, int autoreset,
                    const uint8_t *sprites_rgba, int sw, int sh, uint8_t *frames, int nthreads);
+/* Frames of n given states (the arrays of tgo_step_states; no stream is needed), on at most 16
+ * threads: tgo_env_set_state, then tgo_render, per state.  frames [n][H*48][W*48][3].  Returns
+ * the OR of the tgo_render codes (0 or 1), or -1 on any failure. */
+int tgo_render_states(const tgo_level *lv, int64_t n, const int32_t *pos, const uint32_t *flags,
+                      const int32_t *objs, const double *ang, const uint8_t *sprites_rgba, int sw,
+                      int sh, uint8_t *frames, int nthreads);
 /* Random(seed).choice over a sequence of length n, `count` times (DR/:83-86) */
 void tgo_choice_seq(uint64_t seed, int n, int count, int32_t *out);
 

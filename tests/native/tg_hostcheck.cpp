@@ -27,6 +27,62 @@ uint64_t rec_hash(uint64_t h, const double o[9], int32_t r, int v, int d) {
   }
   return sm64(h ^ ((uint64_t)(uint32_t)r | ((uint64_t)v << 32) | ((uint64_t)d << 40)));
 }
+
+// The renderer's tables for one level and sprite sheet, built by tg_render_init's host code, and
+// one frame composed from an env's state words exactly as k_render's lanes do it (band by band,
+// row by row, 16-B chunk by chunk).  The one copy of that loop: hc_render_run and
+// hc_render_states differ only in how they reach the state words.
+struct HostFrames {
+  std::vector<uint8_t> bg, tiles;
+  std::vector<uint32_t> dyn;
+  RenderArgs A;
+  HostFrames(const HostLevel& hl, const uint8_t* sprites, int sw, int sh) {
+    const Level& L = hl.L;
+    std::vector<std::string> desc;
+    for (auto& l : lines_of(hl.dom)) desc.push_back(strip(l));
+    while (!desc.empty() && desc.back().empty()) desc.pop_back();
+    const std::vector<uint32_t> sc = scale_sprites(sprites, sw, sh);
+    const std::vector<uint32_t> bg32 = static_layer(desc, L.W, L.H, sc);
+    bg = rgb_bytes(bg32);
+    dyn = dynamic_sprites(sc);
+    tiles = rgb_bytes(cell_tiles(bg32, L.W, L.H, dyn));
+    A.bg = reinterpret_cast<const uint4*>(bg.data());
+    A.tiles = reinterpret_cast<const uint4*>(tiles.data());
+    A.spr = dyn.data();
+    A.err = nullptr;  // the error bits are frame()'s return value
+    render_level(L, A);
+  }
+  HostFrames(const HostFrames&) = delete;
+  HostFrames& operator=(const HostFrames&) = delete;
+  size_t frame_bytes() const { return (size_t)A.Hpx * A.Wpx * 3; }
+  // frame [H*48][W*48][3]; returns the TG_ERR_RENDER bits
+  uint32_t frame(const uint4 st, const double2 an, uint8_t* frame) const {
+    uint32_t err = 0;
+    uint4* out = reinterpret_cast<uint4*>(frame);
+    std::vector<uint16_t> sel((size_t)A.W);
+    for (int band = 0; band < A.H; ++band) {
+      const int ylo = band * RS;
+      Layer lay[NLAYER];
+      uint32_t live_mask = 0;
+      for (int k = 0; k < NLAYER; ++k) {
+        bool live = false;
+        err |= make_layer(A, k, st, an, lay[k], live);
+        live = live && lay[k].y1 > ylo && lay[k].y0 < ylo + RS && lay[k].x1 > 0 && lay[k].x0 < A.Wpx;
+        live_mask |= (uint32_t)live << k;
+      }
+      cell_sources(lay, live_mask, band, A.W, sel.data());
+      for (int r = 0; r < RS; ++r) {
+        const int y = ylo + r;
+        const uint32_t rm = row_items(lay, live_mask, y);
+        for (int q = 0; q < A.CH; ++q) {
+          const uint4 v = A.bg[(size_t)y * A.CH + q];
+          out[(size_t)y * A.CH + q] = rm ? render_chunk(A, lay, rm, sel.data(), band, r, q, v) : v;
+        }
+      }
+    }
+    return err;
+  }
+};
 }  // namespace
 
 extern "C" {
@@ -315,54 +371,53 @@ int hc_render_run(const char* dom, const char* objs, const char* inter, uint64_t
                   int autoreset, const uint8_t* sprites, int sw, int sh, uint8_t* frames) {
   HostLevel hl;
   if (!hl.load(dom, objs, inter, g_gotab, g_masks)) return -1;
-  const Level* L = &hl.L;
-  std::vector<std::string> desc;
-  for (auto& l : lines_of(hl.dom)) desc.push_back(strip(l));
-  while (!desc.empty() && desc.back().empty()) desc.pop_back();
-  const std::vector<uint32_t> sc = scale_sprites(sprites, sw, sh);
-  const std::vector<uint32_t> bg32 = static_layer(desc, L->W, L->H, sc);
-  const std::vector<uint8_t> bg = rgb_bytes(bg32);
-  const std::vector<uint32_t> dyn = dynamic_sprites(sc);
-  const std::vector<uint8_t> tiles = rgb_bytes(cell_tiles(bg32, L->W, L->H, dyn));
-  uint32_t err = 0;
-  RenderArgs A;
-  A.bg = reinterpret_cast<const uint4*>(bg.data());
-  A.tiles = reinterpret_cast<const uint4*>(tiles.data());
-  A.spr = dyn.data();
-  A.err = &err;
-  render_level(*L, A);
+  const HostFrames hf(hl, sprites, sw, sh);
   HostReplay env(hl, false);
-  const size_t fb = (size_t)A.Hpx * A.Wpx * 3;
+  uint32_t err = 0;
   for (int64_t i = 0; i < n; ++i) {
     env.start(seed_base + (uint64_t)envs[i]);
     for (int t = 0; t < steps; ++t) env.step(a0, policy, autoreset != 0, envs[i], t);
     const Env& e = env.e;
-    const uint4 st = pack(e);  // k_render reads the SoA state words
     double2 an;
     an.x = e.ang0, an.y = e.ang1;
-    uint4* out = reinterpret_cast<uint4*>(frames + (size_t)i * fb);
-    for (int band = 0; band < A.H; ++band) {
-      const int ylo = band * RS;
-      Layer lay[NLAYER];
-      uint32_t live_mask = 0;
-      for (int k = 0; k < NLAYER; ++k) {
-        bool live = false;
-        err |= make_layer(A, k, st, an, lay[k], live);
-        live = live && lay[k].y1 > ylo && lay[k].y0 < ylo + RS && lay[k].x1 > 0 && lay[k].x0 < A.Wpx;
-        live_mask |= (uint32_t)live << k;
-      }
-      std::vector<uint16_t> sel((size_t)A.W);
-      cell_sources(lay, live_mask, band, A.W, sel.data());
-      for (int r = 0; r < RS; ++r) {
-        const int y = ylo + r;
-        const uint32_t rm = row_items(lay, live_mask, y);
-        for (int q = 0; q < A.CH; ++q) {
-          const uint4 v = A.bg[(size_t)y * A.CH + q];
-          out[(size_t)y * A.CH + q] = rm ? render_chunk(A, lay, rm, sel.data(), band, r, q, v) : v;
-        }
-      }
-    }
+    err |= hf.frame(pack(e), an, frames + (size_t)i * hf.frame_bytes());  // the SoA state words
   }
+  return (int)err;
+}
+
+// The same composition of n given states (the checkpoint format, case-major arrays as
+// hc_step_states takes them): each goes through the product's codec into the state words
+// k_render reads.  `threads` workers, each on a contiguous share of the cases.
+int hc_render_states(const char* dom, const char* objs, const char* inter, int64_t n,
+                     const int32_t* pos, const uint32_t* flags, const int32_t* cells,
+                     const double* ang, const uint8_t* sprites, int sw, int sh, uint8_t* frames,
+                     int threads) {
+  HostLevel hl;
+  if (!hl.load(dom, objs, inter, g_gotab, g_masks)) return -1;
+  const HostFrames hf(hl, sprites, sw, sh);
+  std::vector<uint32_t> errs(16, 0u);
+  const auto work = [&](int w, int64_t lo, int64_t hi) {
+    for (int64_t i = lo; i < hi; ++i) {
+      Env t{};
+      t.px = pos[2 * i], t.py = pos[2 * i + 1];
+      t.f = flags[i];
+      t.kx = cells[4 * i], t.ky = cells[4 * i + 1], t.gx = cells[4 * i + 2], t.gy = cells[4 * i + 3];
+      double2 an;
+      an.x = ang[2 * i], an.y = ang[2 * i + 1];
+      errs[(size_t)w] |= hf.frame(pack(t), an, frames + (size_t)i * hf.frame_bytes());
+    }
+  };
+  if (threads < 1) threads = 1;
+  if (threads > 16) threads = 16;
+  std::vector<std::thread> pool;
+  const int64_t share = (n + threads - 1) / threads;
+  for (int w = 0; w < threads; ++w) {
+    const int64_t lo = w * share, hi = lo + share < n ? lo + share : n;
+    if (lo < hi) pool.emplace_back(work, w, lo, hi);
+  }
+  for (auto& th : pool) th.join();
+  uint32_t err = 0;
+  for (uint32_t e : errs) err |= e;
   return (int)err;
 }
 

@@ -76,12 +76,13 @@ def read_level(level_dir):
     return lv
 
 
-def positions(level_dir):
-    """(ground [H*48, W*48] bool, air likewise): the standing and the airborne positions"""
+def positions(level_dir, door_bits=7):
+    """(ground [H*48, W*48] bool, air likewise): the standing and the airborne positions with
+    the doors of ``door_bits`` closed (all of them unless said otherwise)"""
     import oracle
     lv = read_level(level_dir)
     env = oracle.OracleEnv(0, level_dir)
-    t = env.predicate_table(0, lv["W"] * S, 0, lv["H"] * S, 7)
+    t = env.predicate_table(0, lv["W"] * S, 0, lv["H"] * S, door_bits)
     body = (t & 0x18) == 0x18                      # can_go_left and can_go_right
     fall = (t & 0x20) != 0
     return body & ~fall, body & fall
@@ -102,6 +103,25 @@ def item_cells(lv, bag):
     return key + gold
 
 
+def bag_objs(lv, bag):
+    """objs [n, 4] (key cx, cy, gold cx, cy) of the bag states ``bag`` [n]"""
+    cells = np.array([item_cells(lv, b) for b in range(7)], np.int32)
+    return np.ascontiguousarray(cells[np.asarray(bag)])
+
+
+def pack_flags(facing, doors, handles, bolt, bag):
+    """the checkpoint format's flag words [n] of the given columns (jump_ticker 0)"""
+    def as_u32(a):
+        return np.asarray(a).astype(np.uint32)
+
+    bag = np.asarray(bag)
+    baglen = np.array([len(b) for b in BAGS], np.uint32)
+    items = np.array([sum((c == "G") << j for j, c in enumerate(b)) for b in BAGS], np.uint32)
+    return (as_u32(facing) << sc.F_FACING | as_u32(doors) << sc.F_OBJ
+            | as_u32(handles) << (sc.F_OBJ + 3) | as_u32(bolt) << (sc.F_OBJ + 5)
+            | baglen[bag] << sc.F_BAGLEN | items[bag] << sc.F_BAGITEM)
+
+
 class Sweep:
     """n cases: the columns below, and ``states(lo, hi)`` / ``actions``"""
     COLS = ("px", "py", "doors", "handles", "bolt", "bag", "facing", "action")
@@ -116,14 +136,8 @@ class Sweep:
         self.n = n
         self.cx = self.px // S
         self.cy = (self.py + S // 2) // S
-        cells = np.array([item_cells(self.lv, b) for b in range(7)], np.int32)
-        self.objs = np.ascontiguousarray(cells[self.bag])
-        baglen = np.array([len(b) for b in BAGS], np.uint32)
-        items = np.array([sum((c == "G") << j for j, c in enumerate(b)) for b in BAGS], np.uint32)
-        f = (self.facing.astype(np.uint32) << sc.F_FACING | self.doors.astype(np.uint32) << sc.F_OBJ
-             | self.handles.astype(np.uint32) << (sc.F_OBJ + 3)
-             | self.bolt.astype(np.uint32) << (sc.F_OBJ + 5)
-             | baglen[self.bag] << sc.F_BAGLEN | items[self.bag] << sc.F_BAGITEM)
+        self.objs = bag_objs(self.lv, self.bag)
+        f = pack_flags(self.facing, self.doors, self.handles, self.bolt, self.bag)
         self.flags = np.ascontiguousarray(f, np.uint32)   # jump_ticker 0
         self.pos = np.ascontiguousarray(np.stack([self.px, self.py], 1), np.int32)
         up = np.stack([self.handles & 1, self.handles >> 1 & 1], 1)

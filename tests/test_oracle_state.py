@@ -1,5 +1,6 @@
 """State injection on the C oracle (tgo_env_set_state / tgo_env_get_state, the tick-limited
-step and the threaded oracle.step_states), pinned on the CPU before the sweeps rely on it:
+step, the threaded oracle.step_states and oracle.render_states), pinned on the CPU before the
+sweeps rely on it:
 against the reference's recorded fixtures, and against the Python restatement (oracle/pyref.py
 through state_codec.inject_pyref) on synthesized states under the same tick limit."""
 import glob
@@ -166,3 +167,54 @@ def test_step_states_match_the_restatement(oracle, name, count):
         ran += r is not None
         ncap += capped
     assert ran >= count // 10 and ncap >= 1   # the sample runs options, and meets the limit
+
+
+def _sprites(seed):
+    from gym_treasure_game_amd import render as R
+    return R.synthetic_sprites(seed=seed)
+
+
+@pytest.mark.parametrize("name", [None, "render_overlap", "narrow"])
+def test_render_states_is_set_state_then_render(oracle, name):
+    """the threaded oracle.render_states against OracleEnv.set_state + render, frame by frame,
+    on the first 40 cases of the (permuted) render sweep"""
+    import render_sweep as rs
+    sw = rs.sweep(name)
+    sprites = _sprites(17)
+    st = sw.states(0, 40, mt=False)
+    frames = oracle.render_states(st, sprites, level_dir=sw.level_dir)
+    assert frames.shape == (40, sw.lv["H"] * 48, sw.lv["W"] * 48, 3) and frames.dtype == np.uint8
+    env = oracle.OracleEnv(99, sw.level_dir)
+    for i in range(40):
+        env.set_state({k: st[k][i] for k in ("pos", "flags", "objs", "ang")})
+        assert np.array_equal(env.render(sprites), frames[i]), sw.describe(i)
+    assert len({f.tobytes() for f in frames}) == 40
+    one = oracle.render_states(st, sprites, level_dir=sw.level_dir, nthreads=1)
+    assert np.array_equal(one, frames)
+
+
+@pytest.mark.parametrize("name,policy,autoreset,a0", [(None, 1, True, 0x51), ("corridor", 1, True, 9),
+                                                      ("render_overlap", 1, True, 5),
+                                                      (None, 0, False, 0x52)])
+def test_render_states_of_replayed_envs_is_run_render(oracle, name, policy, autoreset, a0):
+    """envs replayed as run_render replays them (seed base 0, the run() action stream):
+    render_states(get_state()) is run_render's frame, at a few step counts; this ties the new
+    entry point to every pin of run_render"""
+    import render_sweep as rs
+    level_dir = rs.LEVELS[name] if name else None
+    sprites = _sprites(23)
+    envs = np.arange(6) * 5
+    for steps in (0, 7, 33):
+        rows = []
+        for g in envs.tolist():
+            env = oracle.OracleEnv(g, level_dir)
+            for t in range(steps):
+                m = env.mask() if policy else 0
+                _, _, d, _ = env.step(oracle.pick_action(a0, g, t, bool(policy), m))
+                if d and autoreset:
+                    env.reset()
+            rows.append(env.get_state())
+        st = {k: np.stack([r[k] for r in rows]) for k in ("pos", "flags", "objs", "ang")}
+        got = oracle.render_states(st, sprites, level_dir=level_dir)
+        want = oracle.run_render(0, envs, steps, a0, policy, autoreset, sprites, level_dir=level_dir)
+        assert np.array_equal(got, want), (name, steps)
