@@ -45,7 +45,8 @@ EXPORTS = ("tg_create", "tg_destroy", "tg_num_envs", "tg_reset", "tg_step", "tg_
            "tg_observe", "tg_policy_actions", "tg_episodes", "tg_errors", "tg_set_mode", "tg_set_timing", "tg_regenerate",
            "tg_set_episode_capacity", "tg_predicate_table",
            "tg_get_stats", "tg_stats_reset", "tg_kernel_info", "tg_mt_layout", "tg_probe_dispatch", "tg_live_resources", "tg_read_state", "tg_write_state", "tg_render_init", "tg_frame_shape",
-           "tg_render", "tg_frame_shape_scaled", "tg_render_scaled", "tg_policy_mlp_load", "tg_policy_mlp",
+           "tg_render", "tg_frame_shape_scaled", "tg_render_scaled", "tg_frame_shape_view", "tg_render_view",
+           "tg_policy_mlp_load", "tg_policy_mlp",
            "tg_rollout_mlp", "tg_last_error", "tg_version")
 
 
@@ -132,6 +133,8 @@ def load():
         "tg_render": (i32, [P, i64, i64, P, P]),
         "tg_frame_shape_scaled": (i32, [P, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]),
         "tg_render_scaled": (i32, [P, i64, i64, i32, i32, P, P]),
+        "tg_frame_shape_view": (i32, [P, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]),
+        "tg_render_view": (i32, [P, i64, i64, i32, i32, i32, P, P, P]),
         "tg_policy_mlp_load": (i32, [P, i32, i32, i32, P, P]),
         "tg_policy_mlp": (i32, [P, u64, i64, i32, P, P, P, P, P]),
         "tg_rollout_mlp": (i32, [P, i32, u64, i64, i32, u32, P, P, P, P, P, P, P, P]),

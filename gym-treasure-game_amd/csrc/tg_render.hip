@@ -36,6 +36,7 @@
 #include "tg_level.h"
 #include "tg_render.h"
 #include "tg_render_scaled.h"
+#include "tg_render_view.h"
 
 namespace tg {
 
@@ -253,6 +254,139 @@ __global__ __launch_bounds__(RBLOCK) void k_render_scaled(ScaledArgs P,
   }
 }
 
+// ---- tg_render_view ------------------------------------------------------------------------
+// The window of (2r+1) x (2r+1) cells around each env's hero (tg_render_view.h), n x n output
+// pixels.  k_render_scaled's three passes over a span of VSPAN output pixels of a group's run
+// of frames, with what a window changes:
+//   * a window frame is 9 B to 1.5 MB, so the group is G = view_group(n * n) envs, a multiple
+//     of 4: 12 frames of 18 x 18 fill one span, one frame of 720 x 720 takes 127 spans;
+//   * a workgroup makes the Layers of the envs its span touches only (one env of the 4 at
+//     r = 7, scale 1), yet every env's nine items pass make_layer in some workgroup, so
+//     TG_ERR_RENDER is raised as tg_render_scaled raises it; the workgroup holding an env's
+//     first pixel writes its origin;
+//   * the items are culled against the window, not the frame: a handle outside it costs
+//     nothing after its make_layer;
+//   * a window pixel outside the frame is 0 and forms no table index (view_map);
+//   * the hero is in every frame: at scale 8 it declines up to 49 of a window's 324 boxes,
+//     where the full frame's 6,552 had the same 49.  The declined boxes are composed one
+//     source row per thread over all 256 threads, as k_render_scaled's pass 2 is, so the
+//     share that matters is divided evenly whatever lanes the hero's pixels fell on; and a
+//     row of a box that the hero alone touches (most of them) takes view_hero_row, which
+//     loads a stretch of the row's static pixels and sprite texels together where
+//     scaled_compose_row waits for one pixel's loads before it asks for the next's.
+// VSPAN, VQCAP, VGMAX and view_group are tg_render_view.h's.  Past VQCAP queued boxes (a span
+// at scale 1 can hold 28 rows of the hero's 48 pixels) a thread composes its own box inline.
+__device__ __forceinline__ void store_px4(const uint32_t* px, int np, int ch, uint8_t* d) {
+  uint32_t c[SPX];
+#pragma unroll
+  for (int j = 0; j < SPX; ++j) c[j] = j < np ? px[j] : 0u;
+  if (ch == 3) {
+    const uint32_t a0 = px3(c[0]), a1 = px3(c[1]), a2 = px3(c[2]), a3 = px3(c[3]);
+    if (np == SPX) {
+      uint32_t* d4 = reinterpret_cast<uint32_t*>(d);
+      d4[0] = a0 | (a1 << 24);
+      d4[1] = (a1 >> 8) | (a2 << 16);
+      d4[2] = (a2 >> 16) | (a3 << 8);
+    } else {
+      const uint32_t a[SPX] = {a0, a1, a2, a3};
+      for (int j = 0; j < np; ++j)
+        for (int b = 0; b < 3; ++b) d[3 * j + b] = (uint8_t)(a[j] >> (8 * b));
+    }
+  } else {
+    const uint32_t g0 = luma_px(c[0]), g1 = luma_px(c[1]), g2 = luma_px(c[2]), g3 = luma_px(c[3]);
+    if (np == SPX) {
+      *reinterpret_cast<uint32_t*>(d) = g0 | (g1 << 8) | (g2 << 16) | (g3 << 24);
+    } else {
+      const uint32_t a[SPX] = {g0, g1, g2, g3};
+      for (int j = 0; j < np; ++j) d[j] = (uint8_t)a[j];
+    }
+  }
+}
+
+__global__ __launch_bounds__(RBLOCK) void k_render_view(ViewArgs V, const uint4* __restrict__ st4,
+                                                        const double2* __restrict__ angs,
+                                                        int64_t first, int64_t count, int G,
+                                                        int spans, uint8_t* __restrict__ out,
+                                                        int32_t* __restrict__ origin) {
+  __shared__ Layer lay[VGMAX][NLAYER];
+  __shared__ uint32_t live[VGMAX];
+  __shared__ int org[VGMAX][2];              // each env's window origin in cells
+  __shared__ uint32_t px[VSPAN];             // the span's pixels, XRGB
+  __shared__ unsigned long long acc[VQCAP];  // a queued box's channel sums
+  __shared__ uint16_t queue[VQCAP];          // its pixel within the span
+  __shared__ uint32_t qn;
+  const ScaledArgs& P = V.P;
+  const int tid = (int)threadIdx.x;
+  const int64_t grp = blockIdx.x / spans;
+  const int span = (int)(blockIdx.x - grp * spans);
+  const int64_t e0 = grp * G;
+  const int ne = (int)(count - e0 < G ? count - e0 : G);
+  const int fp = V.n * V.n;  // output pixels per frame
+  const int gpx = ne * fp;   // and in this group
+  const int pb = span * VSPAN;
+  if (pb >= gpx) return;     // a short last group needs fewer spans (block-uniform)
+  const int npx = gpx - pb < VSPAN ? gpx - pb : VSPAN;
+  const int k0 = pb / fp, nk = (pb + npx - 1) / fp - k0 + 1;  // the envs this span touches
+  if (tid < VGMAX) live[tid] = 0u;
+  if (tid == 0) qn = 0u;
+  for (int e = tid; e < VQCAP; e += RBLOCK) acc[e] = 0ull;
+  __syncthreads();
+  if (tid < nk * NLAYER) {
+    const int k = k0 + tid / NLAYER, i = tid % NLAYER;
+    const int64_t g = first + e0 + k;
+    const uint4 st = st4[g];
+    int ox, oy;
+    view_origin(st, V.r, ox, oy);
+    Layer l;
+    bool on = false;
+    const uint32_t err = make_layer(P.A, i, st, angs[g], l, on);
+    if (err) atomicOr(P.A.err, err);
+    if (on && l.x1 > 0 && l.x0 < P.A.Wpx && l.y1 > 0 && l.y0 < P.A.Hpx &&
+        view_overlaps(l, ox, oy, V.r)) {
+      lay[k][i] = l;
+      atomicOr(&live[k], 1u << i);
+    }
+    if (i == NLAYER - 1) {
+      org[k][0] = ox, org[k][1] = oy;
+      if (origin && k * fp >= pb) origin[2 * (e0 + k)] = ox, origin[2 * (e0 + k) + 1] = oy;
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < npx; i += RBLOCK) {
+    int k, vx, vy, x, y;
+    span_pixel(pb + i, fp, V.n, k, vx, vy);
+    uint32_t c = 0u;
+    if (view_map(P, org[k][0], org[k][1], vx, vy, x, y)) {
+      const uint32_t hit = pixel_items(P, lay[k], live[k], x, y);
+      if (!scaled_lookup(P, lay[k], live[k], hit, x, y, c)) {
+        const uint32_t slot = atomicAdd(&qn, 1u);
+        if (slot < (uint32_t)VQCAP) {
+          queue[slot] = (uint16_t)i;
+          continue;
+        }
+        c = view_compose(P.A, lay[k], hit, P.s, x, y);
+      }
+    }
+    px[i] = c;
+  }
+  __syncthreads();
+  const int nq = (int)(qn < (uint32_t)VQCAP ? qn : (uint32_t)VQCAP);
+  for (int wi = tid; wi < nq * P.s; wi += RBLOCK) {
+    const int e = wi / P.s, dy = wi - e * P.s;
+    int k, vx, vy, x, y;
+    span_pixel(pb + queue[e], fp, V.n, k, vx, vy);
+    view_map(P, org[k][0], org[k][1], vx, vy, x, y);  // queued: inside the frame
+    const uint32_t hit = pixel_items(P, lay[k], live[k], x, y);
+    atomicAdd(&acc[e], (unsigned long long)view_compose_row(P.A, lay[k], hit, P.s, x, P.s * y + dy));
+  }
+  __syncthreads();
+  for (int e = tid; e < nq; e += RBLOCK) px[queue[e]] = scaled_finish(acc[e], P.s);
+  __syncthreads();
+  uint8_t* const gout = out + (e0 * (int64_t)fp + pb) * P.ch;
+  for (int i0 = tid * SPX; i0 < npx; i0 += RBLOCK * SPX)
+    store_px4(px + i0, npx - i0 < SPX ? npx - i0 : SPX, P.ch, gout + (int64_t)i0 * P.ch);
+}
+
 }  // namespace
 }  // namespace tg
 
@@ -273,6 +407,27 @@ static int check_frames(const tg_batch* h, const char* who, int64_t first, int64
     return fail(TG_E_INVAL, "%s: envs [%lld, %lld) outside [0, %lld)", who, (long long)first,
                 (long long)(first + count), (long long)h->n);
   if (((uintptr_t)out & 15u) != 0) return fail(TG_E_INVAL, "%s: the output must be 16-B aligned", who);
+  return TG_OK;
+}
+
+// The scaled kernels' arguments at `scale` (scale_index si).  A scale's first call, from
+// tg_render_scaled or tg_render_view, pools the static layer and the cell tiles on the host and
+// uploads them (it synchronises); later calls read the cache.
+static int scaled_args(tg_batch* h, int si, int32_t scale, int32_t channels, ScaledArgs& P) {
+  RenderState* rs = h->rs.get();
+  const int W = h->L.W, H = h->L.H;
+  if (!rs->bg_small[si]) {
+    const std::vector<uint32_t> b = pooled_static(rs->bg32, W, H, scale);
+    const std::vector<uint32_t> t = pooled_tiles(rs->bg32, W, H, rs->dyn, scale);
+    DevBuf<uint32_t> db, dt;  // installed once both are uploaded
+    TG_TRY(db.upload(b.data(), b.size(), "a scale's static layer"));
+    TG_TRY(dt.upload(t.data(), t.size(), "a scale's cell tiles"));
+    rs->bg_small[si] = std::move(db), rs->tiles_small[si] = std::move(dt);
+  }
+  P.A = render_args(h);
+  P.bg_small = rs->bg_small[si].get(), P.tiles_small = rs->tiles_small[si].get();
+  P.s = scale, P.cs = RS / scale, P.w = P.A.Wpx / scale, P.h = P.A.Hpx / scale;
+  P.ch = channels, P.fast = 1;  // fast: scaled_pixel's switch (host check); the kernels have none
   return TG_OK;
 }
 
@@ -356,21 +511,8 @@ int tg_render_scaled(tg_batch* h, int64_t first, int64_t count, int32_t scale, i
     return fail(TG_E_INVAL, "tg_render_scaled: channels must be TG_FRAME_RGB or TG_FRAME_GRAY");
   TG_TRY(check_frames(h, "tg_render_scaled", first, count, out));
   if (!count) return TG_OK;
-  RenderState* rs = h->rs.get();
-  const int W = h->L.W, H = h->L.H;
-  if (!rs->bg_small[si]) {  // this scale's first call: pool on the host, upload (synchronises)
-    const std::vector<uint32_t> b = pooled_static(rs->bg32, W, H, scale);
-    const std::vector<uint32_t> t = pooled_tiles(rs->bg32, W, H, rs->dyn, scale);
-    DevBuf<uint32_t> db, dt;  // installed once both are uploaded
-    TG_TRY(db.upload(b.data(), b.size(), "a scale's static layer"));
-    TG_TRY(dt.upload(t.data(), t.size(), "a scale's cell tiles"));
-    rs->bg_small[si] = std::move(db), rs->tiles_small[si] = std::move(dt);
-  }
   ScaledArgs P;
-  P.A = render_args(h);
-  P.bg_small = rs->bg_small[si].get(), P.tiles_small = rs->tiles_small[si].get();
-  P.s = scale, P.cs = RS / scale, P.w = P.A.Wpx / scale, P.h = P.A.Hpx / scale;
-  P.ch = channels, P.fast = 1;  // fast: scaled_pixel's switch (host check); the kernel has none
+  TG_TRY(scaled_args(h, si, scale, channels, P));
   const int64_t group_px = (int64_t)SG * P.h * P.w;
   if (group_px > 0x7FFFFFFF - SSPAN)
     return fail(TG_E_INVAL, "tg_render_scaled: frame too large at this scale");
@@ -379,6 +521,46 @@ int tg_render_scaled(tg_batch* h, int64_t first, int64_t count, int32_t scale, i
   if (blocks > 0x7FFFFFFF) return fail(TG_E_INVAL, "tg_render_scaled: too many envs in one call");
   hipLaunchKernelGGL(k_render_scaled, dim3((unsigned)blocks), dim3(RBLOCK), 0, (hipStream_t)stream,
                      P, h->S.st4, h->S.ang, first, count, spans, out);
+  HIP_TRY(hipGetLastError());
+  return TG_OK;
+}
+
+static int view_dims(const tg_batch* h, int32_t radius, int32_t scale, int* si) {
+  TG_TRY(scaled_dims(h, scale, si));
+  if (radius < 1 || radius > VIEW_RMAX)
+    return fail(TG_E_INVAL, "radius %d is outside 1..%d", (int)radius, VIEW_RMAX);
+  return TG_OK;
+}
+
+int tg_frame_shape_view(const tg_batch* h, int32_t radius, int32_t scale, int32_t* height,
+                        int32_t* width) {
+  int si;
+  TG_TRY(view_dims(h, radius, scale, &si));
+  if (height) *height = RS * (2 * radius + 1) / scale;
+  if (width) *width = RS * (2 * radius + 1) / scale;
+  return TG_OK;
+}
+
+int tg_render_view(tg_batch* h, int64_t first, int64_t count, int32_t radius, int32_t scale,
+                   int32_t channels, uint8_t* out, int32_t* origin, void* stream) {
+  BIND(h);
+  if (!h->rs) return fail(TG_E_STATE, "tg_render_view: call tg_render_init first");
+  int si;
+  TG_TRY(view_dims(h, radius, scale, &si));
+  if (channels != TG_FRAME_RGB && channels != TG_FRAME_GRAY)
+    return fail(TG_E_INVAL, "tg_render_view: channels must be TG_FRAME_RGB or TG_FRAME_GRAY");
+  TG_TRY(check_frames(h, "tg_render_view", first, count, out));
+  if (!count) return TG_OK;
+  ViewArgs V;
+  TG_TRY(scaled_args(h, si, scale, channels, V.P));
+  V.r = radius, V.n = V.P.cs * (2 * radius + 1);
+  const int fp = V.n * V.n;  // at most 720 * 720
+  const int G = view_group(fp);
+  const int spans = (int)(((int64_t)G * fp + VSPAN - 1) / VSPAN);
+  const int64_t blocks = (count + G - 1) / G * spans;
+  if (blocks > 0x7FFFFFFF) return fail(TG_E_INVAL, "tg_render_view: too many envs in one call");
+  hipLaunchKernelGGL(k_render_view, dim3((unsigned)blocks), dim3(RBLOCK), 0, (hipStream_t)stream, V,
+                     h->S.st4, h->S.ang, first, count, G, spans, out, origin);
   HIP_TRY(hipGetLastError());
   return TG_OK;
 }

@@ -548,7 +548,37 @@ class TreasureGameVec:
                                        _ptr(out), self._stream()), "tg_render_scaled")
         return out
 
-    def render(self, first=0, count=None, out=None, scale=1, gray=False):
+    def frame_shape_view(self, radius, scale=1, gray=False):
+        """(h, w, c) of ``render(view=radius, scale=scale, gray=gray)``'s frames, h = w =
+        48 * (2 * radius + 1) / scale: (18, 18, 1) at radius 1, scale 8, gray.  ``radius`` must
+        be 1..7 and ``scale`` divide 48 (``TgError`` otherwise)."""
+        h, w = ctypes.c_int32(), ctypes.c_int32()
+        check(self._L.tg_frame_shape_view(self.handle, int(radius), int(scale), ctypes.byref(h),
+                                          ctypes.byref(w)), "tg_frame_shape_view")
+        return (h.value, w.value, 1 if gray else 3)
+
+    def _render_view(self, first, count, out, scale, gray, view, origin):
+        if getattr(self, "frame_shape", None) is None:
+            self.render_init()
+        count = self.num_envs - first if count is None else int(count)
+        shape = self.frame_shape_view(view, scale, gray)
+        if out is None:
+            out = torch.empty((max(count, 0),) + shape, dtype=torch.uint8, device=self.device)
+        elif (out.dtype != torch.uint8 or not out.is_contiguous() or out.device != self.device
+              or tuple(out.shape) != (count,) + shape):
+            raise ValueError("out must be a contiguous uint8 [%d, %d, %d, %d] tensor on %s"
+                             % ((count,) + shape + (self.device,)))
+        if origin is not None and (origin.dtype != torch.int32 or not origin.is_contiguous()
+                                   or origin.device != self.device
+                                   or tuple(origin.shape) != (count, 2)):
+            raise ValueError("origin must be a contiguous int32 [%d, 2] tensor on %s"
+                             % (count, self.device))
+        check(self._L.tg_render_view(self.handle, int(first), count, int(view), int(scale),
+                                     shape[2], _ptr(out), None if origin is None else _ptr(origin),
+                                     self._stream()), "tg_render_view")
+        return out
+
+    def render(self, first=0, count=None, out=None, scale=1, gray=False, view=None, origin=None):
         """render('rgb_array') of envs [first, first+count): uint8 [count, H*48, W*48, 3]
         on the device (the reference's ``rgb`` array per env, TG/:103-105).
 
@@ -556,7 +586,17 @@ class TreasureGameVec:
         uint8 [count, H*48/scale, W*48/scale, 3 or 1]: the full frame average-pooled over
         scale x scale boxes (halves round up), then (77 R + 150 G + 29 B + 128) >> 8 for gray,
         rendered directly at that size (tg_render_scaled).  The first call for a scale builds
-        its tables and synchronises."""
+        its tables and synchronises.
+
+        ``view=r`` (1..7) gives the agent-centred window instead (tg_render_view): the
+        (2r+1) x (2r+1) cells around the hero's cell (px // 48, (py + 24) // 48), uint8
+        [count, n, n, 3 or 1] with n = 48 * (2r+1) / scale, the zero-padded crop of the frame
+        ``scale`` and ``gray`` select.  ``origin``, an int32 [count, 2] device tensor, receives
+        each window's origin (ox, oy) in cells."""
+        if view is not None:
+            return self._render_view(first, count, out, scale, gray, view, origin)
+        if origin is not None:
+            raise ValueError("origin is the window's: pass view=radius with it")
         if scale != 1 or gray:
             return self._render_scaled(first, count, out, scale, gray)
         if getattr(self, "frame_shape", None) is None:
@@ -875,13 +915,13 @@ class TreasureGame:
         state, r, done = self._run(a)
         return state, r, done, {}
 
-    def render(self, mode="human", scale=1, gray=False):
+    def render(self, mode="human", scale=1, gray=False, view=None):
         if mode != "rgb_array":
             raise NotImplementedError("render(mode=%r): only 'rgb_array' (no display / gym "
                                       "image viewer here, TG/:106-110)" % (mode,))
         if getattr(self._vec, "frame_shape", None) is None:
             self._vec.render_init(self._sprites)
-        return self._vec.render(scale=scale, gray=gray).cpu().numpy()[0]
+        return self._vec.render(scale=scale, gray=gray, view=view).cpu().numpy()[0]
 
     def close(self):
         if self.viewer is not None:
@@ -901,17 +941,23 @@ class ObservationWrapper:
 
     ``scale`` (a divisor of 48) and ``gray`` select the downscaled / grayscale frame of
     ``TreasureGameVec.render``: [N, 78, 84, 1] at ``scale=8, gray=True`` on the default level
-    (an extension: the reference's wrapper renders full size only).
+    (an extension: the reference's wrapper renders full size only).  ``view=r`` selects the
+    agent-centred window of ``TreasureGameVec.render(view=r)`` at that scale and channel count:
+    [N, 18, 18, 1] at ``scale=8, gray=True, view=1``.
     """
 
-    def __init__(self, env, sprites=None, scale=1, gray=False):
+    def __init__(self, env, sprites=None, scale=1, gray=False, view=None):
         self.env = env
         self._scale, self._gray = int(scale), bool(gray)
+        self._view = None if view is None else int(view)
         self._vec = isinstance(env, TreasureGameVec)
         if self._vec:
             env.render_init(sprites)
-            shape = (env.frame_shape if self._scale == 1 and not self._gray
-                     else env.frame_shape_scaled(self._scale, self._gray))
+            if self._view is not None:
+                shape = env.frame_shape_view(self._view, self._scale, self._gray)
+            else:
+                shape = (env.frame_shape if self._scale == 1 and not self._gray
+                         else env.frame_shape_scaled(self._scale, self._gray))
             self._frames = torch.empty((env.num_envs,) + shape, dtype=torch.uint8,
                                        device=env.device)
         else:
@@ -928,8 +974,10 @@ class ObservationWrapper:
 
     def _screen(self):
         if self._vec:
-            return self.env.render(out=self._frames, scale=self._scale, gray=self._gray)
-        return self.env.render(mode="rgb_array", scale=self._scale, gray=self._gray)
+            return self.env.render(out=self._frames, scale=self._scale, gray=self._gray,
+                                   view=self._view)
+        return self.env.render(mode="rgb_array", scale=self._scale, gray=self._gray,
+                               view=self._view)
 
     def reset(self, **kwargs):
         self.env.reset(**kwargs)

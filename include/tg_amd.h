@@ -394,6 +394,37 @@ int tg_frame_shape_scaled(const tg_batch *h, int32_t scale, int32_t *height, int
 int tg_render_scaled(tg_batch *h, int64_t first, int64_t count, int32_t scale, int32_t channels,
                      uint8_t *out, void *stream);
 
+/* ---- agent-centred windows of the frame (an extension: the reference has no such mode) -----
+ * The hero's cell is the reference's get_player_cell (IM/:441-445) with floor division,
+ *   xc = playerx // 48,  yc = (playery + 24) // 48.
+ * For a `radius` r in 1..7 the window is the (2r+1) x (2r+1) cells with origin
+ * (ox, oy) = (xc - r, yc - r) in cells and side n = 48*(2r+1) pixels.  With F the frame
+ * tg_render writes,
+ *   V[y][x][c] = F[48*oy + y][48*ox + x][c]  where that pixel is inside F, else 0    (y, x < n)
+ * and the output is tg_render_scaled's function of V (the box mean with halves rounded up, then
+ * the gray formula) for `scale` s a divisor of 48.  The origin is cell-aligned and s divides 48,
+ * so every s x s box lies inside one cell of F or wholly outside F: the output equals the
+ * zero-padded crop at (48*oy/s, 48*ox/s), of side n/s, of tg_render_scaled's frame (the gray of
+ * black is 0); scale 1 with TG_FRAME_RGB is that crop of tg_render's frame.  r = 0 is refused:
+ * the hero's 48x48 sprite at (playerx - 24, playery) spans up to 2x3 cells; for r >= 1 it lies
+ * wholly inside the window.  Any position tg_write_state accepts is safe: a window partly or
+ * wholly outside the frame is 0 there.  TG_ERR_RENDER is raised for every env of the range
+ * exactly as by tg_render_scaled, whether or not the offending handle is in the window. */
+/* Output size in pixels: both 48*(2*radius+1)/scale (18 x 18 at radius 1, scale 8). */
+int tg_frame_shape_view(const tg_batch *h, int32_t radius, int32_t scale, int32_t *height,
+                        int32_t *width);
+/* Windows of envs [first, first+count): out u8 [count][n/s][n/s][channels] (device, packed, 16-B
+ * aligned at its start; a frame may be as small as 9 B).  Nothing outside
+ * [out, out + count * frame bytes) is written.  origin may be NULL; otherwise device i32
+ * [count][2] = (ox, oy) in cells, where each window sits in the level.  Needs tg_render_init
+ * first (TG_E_STATE); TG_E_INVAL for a radius outside 1..7, a scale that does not divide 48,
+ * channels other than TG_FRAME_RGB / TG_FRAME_GRAY, a bad range or a misaligned out.  The
+ * first call for a scale builds and caches that scale's pooled tables as tg_render_scaled's
+ * first call does (the same cache: either call warms the other; it synchronises and cannot run
+ * inside a stream capture).  Later calls only launch on `stream`. */
+int tg_render_view(tg_batch *h, int64_t first, int64_t count, int32_t radius, int32_t scale,
+                   int32_t channels, uint8_t *out, int32_t *origin, void *stream);
+
 /* ---- a learned actor on the device (an extension: the reference has no policy) -------------
  * A two-hidden-layer MLP over the 9-dimensional observation with a 9-way policy head and a
  * value head.  Hidden width H is 16, 32, 64 or 128; the activation is TG_ACT_RELU or
