@@ -9,7 +9,8 @@ there is no CPU fallback.  Registration with gym / gymnasium happens on import w
 installed, mirroring gym_treasure_game/__init__.py:3-6.
 """
 from ._lib import TG_ERR_FLOW, TgError  # noqa: F401
-from .envs import (OPTION_NAMES, STATE_NAMES, GpuOption, ObservationWrapper,  # noqa: F401
+from .envs import (DONE_TERMINATED, DONE_TRUNCATED, OPTION_NAMES, STATE_NAMES,  # noqa: F401
+                   GpuOption, ObservationWrapper,
                    TreasureGame, TreasureGameVec, TreasureGameVectorEnv, make_vec,
                    mlp_param_count, pack_mlp_params, read_level)
 from .render import load_sprites, synthetic_sprites  # noqa: F401

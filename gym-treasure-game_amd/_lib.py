@@ -13,6 +13,9 @@ LIB_PATH = os.environ.get("TG_LIB_PATH") or os.path.join(HERE, "libtg_amd.so")
 
 TG_OK = 0
 TG_STEP_AUTORESET = 1
+TG_DONE_TERMINATED = 1
+TG_DONE_TRUNCATED = 2
+TG_EPISODE_TRUNCATED = 1 << 30
 TG_POLICY_UNIFORM = 0
 TG_POLICY_MASKED = 1
 TG_MODE_DIRECT = 0
@@ -43,7 +46,7 @@ EXPORTS = ("tg_create", "tg_destroy", "tg_num_envs", "tg_reset", "tg_step", "tg_
            "tg_reset1_py", "tg_set_serve", "tg_step1_pywords", "tg_available_mask1", "tg_reset1", "tg_rollout", "tg_set_groups",
            "tg_available_mask",
            "tg_observe", "tg_policy_actions", "tg_episodes", "tg_errors", "tg_set_mode", "tg_set_timing", "tg_regenerate",
-           "tg_set_episode_capacity", "tg_predicate_table",
+           "tg_set_episode_capacity", "tg_set_time_limit", "tg_predicate_table",
            "tg_get_stats", "tg_stats_reset", "tg_kernel_info", "tg_mt_layout", "tg_probe_dispatch", "tg_live_resources", "tg_read_state", "tg_write_state", "tg_render_init", "tg_frame_shape",
            "tg_render", "tg_frame_shape_scaled", "tg_render_scaled", "tg_frame_shape_view", "tg_render_view",
            "tg_policy_mlp_load", "tg_policy_mlp",
@@ -73,7 +76,8 @@ class Stats(ctypes.Structure):
                 ("wave_ticks", ctypes.c_int64), ("timed_launches", ctypes.c_int64),
                 ("run_ms", ctypes.c_double), ("regen_ms", ctypes.c_double),
                 ("regen_timed", ctypes.c_int64), ("regen_launches", ctypes.c_int64),
-                ("classify_ms", ctypes.c_double), ("regens_quiet", ctypes.c_int64)]
+                ("classify_ms", ctypes.c_double), ("regens_quiet", ctypes.c_int64),
+                ("episodes_truncated", ctypes.c_int64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -117,6 +121,7 @@ def load():
         "tg_set_timing": (i32, [P, i32]),
         "tg_regenerate": (i32, [P, P]),
         "tg_set_episode_capacity": (i32, [P, i32]),
+        "tg_set_time_limit": (i32, [P, i32]),
         "tg_predicate_table": (i32, [P, i32, i32, i32, i32, u32, P, P]),
         "tg_get_stats": (i32, [P, ctypes.POINTER(Stats)]),
         "tg_stats_reset": (i32, [P]),

@@ -1,7 +1,8 @@
 // tg_amd.hip — MI355X (gfx950) batched Treasure Game: the host code and the C ABI of
 // include/tg_amd.h.  The kernels it launches are in the headers it includes: tg_dev.h (the device
 // layer shared with k_flow's unit, tg_flow.hip; the state layout is described there),
-// tg_kernels.h (the batch kernels), tg_py1.h (the N = 1 path) and tg_flow.h (TG_MODE_FLOW's
+// tg_kernels.h (the batch kernels), tg_timelimit.h (the step limit's kernel), tg_py1.h (the N = 1
+// path) and tg_flow.h (TG_MODE_FLOW's
 // types; k_flow itself is instantiated by tg_flow.hip and launched through tg::flow_launch).
 #include <hip/hip_runtime.h>
 
@@ -22,6 +23,7 @@
 #include "tg_flow.h"
 #include "tg_kernels.h"
 #include "tg_py1.h"
+#include "tg_timelimit.h"
 
 namespace tg {
 thread_local std::string g_err;
@@ -246,7 +248,15 @@ int launch_step(tg_batch* h, StepCtx& c, const StepIO& io_in, bool ar, hipStream
                        c.n, h->L, lgrid, io, q, w, g0, stats, err, ks1);
   }
   HIP_TRY(hipGetLastError());
-  if (h->mode != TG_MODE_DIRECT && ++c.rpend == REGEN_STEPS) return launch_regen(h, c, st);
+  if (h->mode != TG_MODE_DIRECT && ++c.rpend == REGEN_STEPS) TG_TRY(launch_regen(h, c, st));
+  // the step limit (tg_set_time_limit), after everything else of the step: where a tg_reset
+  // between this step and the next would stand (its block b counts in stats slot b < stat_slots)
+  if (h->time_limit) {
+    const auto kt = ar ? &k_timelimit<true> : &k_timelimit<false>;
+    hipLaunchKernelGGL(kt, grid, block, 0, st, S, c.n, h->L, h->time_limit, tstep, io.obs, io.done, q,
+                       g0, stats, err);
+    HIP_TRY(hipGetLastError());
+  }
   return TG_OK;
 }
 
@@ -851,6 +861,14 @@ int tg_set_groups(tg_batch* h, int32_t groups, int32_t stagger) {
   return TG_OK;
 }
 
+int tg_set_time_limit(tg_batch* h, int32_t max_steps) {
+  BIND(h);
+  if (max_steps < 0 || max_steps >= TG_EPISODE_TRUNCATED)
+    return fail(TG_E_INVAL, "tg_set_time_limit: max_steps %d (0 = off, 1 .. 2^30 - 1)", max_steps);
+  h->time_limit = (uint32_t)max_steps;
+  return TG_OK;
+}
+
 int tg_set_episode_capacity(tg_batch* h, int32_t cap) {
   BIND(h);
   if (cap < 1 || cap > (1 << 28)) return fail(TG_E_INVAL, "tg_set_episode_capacity: cap %d", cap);
@@ -886,6 +904,10 @@ int tg_rollout(tg_batch* h, int32_t steps, uint64_t action_seed, int64_t t0, int
                uint32_t flags, int32_t* actions, double* obs, int32_t* reward, uint8_t* valid,
                uint8_t* done, void* stream) {
   BIND(h);
+  if (h->mode == TG_MODE_FLOW && h->time_limit)
+    return fail(TG_E_INVAL, "tg_rollout: TG_MODE_FLOW runs its steps inside k_flow, which has no step "
+                            "boundary for tg_set_time_limit's limit; use TG_MODE_COMPACT or "
+                            "TG_MODE_DIRECT, or tg_step");
   if (steps == 0) return TG_OK;
   TG_TRY(rollout_prep(h, "tg_rollout", steps, policy == TG_POLICY_UNIFORM || policy == TG_POLICY_MASKED,
                       obs, reward, valid, done));
@@ -1282,6 +1304,7 @@ int tg_get_stats(tg_batch* h, tg_stats* out) {
   out->regen_timed = t.regen_timed;
   out->regen_launches = t.regen_launches;
   out->classify_ms = t.classify_ms;
+  out->episodes_truncated = (int64_t)s[ST_TRUNC];
   return TG_OK;
 }
 

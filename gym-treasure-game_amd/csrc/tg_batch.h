@@ -334,6 +334,7 @@ struct tg_batch {
   tg::Event fork;                  //   the groups' fork event
   bool stagger = false;            //   group g + 1 starts after group g's first k_classify
   uint32_t tstep = 0;  // steps taken by the handle (mod 2^32): S.ep holds each episode's start step
+  uint32_t time_limit = 0;  // tg_set_time_limit: k_timelimit after every step's kernels (0: off)
   int regen_per_cu = 0;  // k_regen workgroups resident per CU (occupancy API, first use)
   tg::Timing tm;
   tg::Mlp mlp;

@@ -426,6 +426,7 @@ __device__ __forceinline__ int wave_sum(int v) {
 
 enum { ST_STEPS, ST_VALID, ST_TICKS, ST_DRAWS, ST_EPISODES, ST_EP_OVERFLOW, ST_REGENS, ST_WTICKS,
        ST_RQUIET,  // of ST_REGENS, the halves of k_run's quiet drain
+       ST_TRUNC,   // of ST_EPISODES, those a step limit ended (k_timelimit, tg_timelimit.h)
        ST_COUNT };
 
 // 64-lane max (wave64)

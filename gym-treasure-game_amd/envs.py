@@ -25,6 +25,9 @@ OPTION_NAMES = ["go_left_option", "go_right_option", "up_ladder_option", "down_l
 STATE_NAMES = ["playerx", "playery", "handle1.angle", "handle2.angle", "key.x", "key.y",
                "bolt.locked", "goldcoin.x", "goldcoin.y"]  # get_state_descriptors (IM/:380-400)
 LEVEL_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "levels", "default")
+# bits of a done row: the env's own end (the only bit without a step limit), and the step limit's
+DONE_TERMINATED = _lib.TG_DONE_TERMINATED
+DONE_TRUNCATED = _lib.TG_DONE_TRUNCATED
 
 
 # ---- spaces: gym's / gymnasium's when importable, else minimal stand-ins with the same fields
@@ -178,10 +181,16 @@ class TreasureGameVec:
     never resets by itself; this is the equivalent of calling ``reset()`` right after), its
     pre-reset obs goes to ``info["final_obs"]`` and its episode (return, length) to
     ``episodes()``.
+    ``max_episode_steps`` (``set_time_limit``) truncates episodes at that many steps on the
+    device, in ``step`` and inside ``rollout``: ``done`` is then a bit set, ``DONE_TERMINATED``
+    (1, the only value without a limit) and ``DONE_TRUNCATED`` (2).  With auto-reset a truncated
+    env is reset in the same step as a terminated one is and its episode is queued with the
+    truncated flag (``episodes(truncated=True)``); without, it is only flagged, at every step
+    from the limit on.
     """
 
     def __init__(self, num_envs, seed=0, device=None, global_offset=0, autoreset=False,
-                 level_dir=None, copy=False, mode="compact"):
+                 level_dir=None, copy=False, mode="compact", max_episode_steps=None):
         if not torch.cuda.is_available():
             raise TgError("TreasureGameVec needs a ROCm GPU (gfx950); there is no CPU path")
         self._L = _lib.load()
@@ -222,6 +231,9 @@ class TreasureGameVec:
         self._mode = "compact"
         if mode != "compact":
             self.set_mode(mode)
+        self.max_episode_steps = None
+        if max_episode_steps is not None:
+            self.set_time_limit(max_episode_steps)
 
     # -- plumbing ---------------------------------------------------------------------------
     def _stream(self):
@@ -292,6 +304,9 @@ class TreasureGameVec:
         not valid: with ``check_flow`` (the default) the call then synchronises on
         ``errors()`` and raises TgError."""
         k, n, dev = int(steps), self.num_envs, self.device
+        if self._mode == "flow" and self.max_episode_steps is not None:
+            raise TgError("rollout() in the flow mode cannot apply max_episode_steps (k_flow has "
+                          "no step boundary): use the compact or direct mode, or step()")
         out = {"reward": torch.empty((k, n), dtype=torch.int32, device=dev),
                "valid": torch.empty((k, n), dtype=torch.uint8, device=dev),
                "done": torch.empty((k, n), dtype=torch.uint8, device=dev)}
@@ -427,20 +442,27 @@ class TreasureGameVec:
                                   self._stream()), "tg_episodes")
 
     @staticmethod
-    def decode_episodes(rows):
-        """raw tg_episode rows (int64 [k, 2]) -> int64 [k, 3] = (env, return, length)."""
+    def decode_episodes(rows, truncated=False):
+        """raw tg_episode rows (int64 [k, 2]) -> int64 [k, 3] = (env, return, length), the step
+        limit's flag stripped from the length; ``truncated=True``: [k, 4], the last column 1 for
+        an episode the step limit ended."""
         packed = rows[:, 1]
         ret = ((packed & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000  # sign-extend the i32 half
-        return torch.stack([rows[:, 0], ret, packed >> 32], dim=1)
+        ln = packed >> 32
+        cols = [rows[:, 0], ret, ln & (_lib.TG_EPISODE_TRUNCATED - 1)]
+        if truncated:
+            cols.append(((ln & _lib.TG_EPISODE_TRUNCATED) != 0).to(torch.int64))
+        return torch.stack(cols, dim=1)
 
-    def episodes(self, cap=None):
+    def episodes(self, cap=None, truncated=False):
         """Completed (auto-reset) episodes, oldest first, up to ``cap`` of them:
-        int64 [k, 3] = (global env, return, length) on the device (synchronises)."""
+        int64 [k, 3] = (global env, return, length) on the device (synchronises);
+        ``truncated=True`` adds a column, 1 for an episode the step limit ended."""
         cap = self.num_envs if cap is None else int(cap)
         rec = torch.empty((max(cap, 1), 2), dtype=torch.int64, device=self.device)
         cnt = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.drain_episodes(rec[:cap], cnt)
-        return self.decode_episodes(rec[: int(cnt.item())])
+        return self.decode_episodes(rec[: int(cnt.item())], truncated)
 
     def errors(self):
         v = ctypes.c_uint32(0)
@@ -461,6 +483,14 @@ class TreasureGameVec:
              "flow": _lib.TG_MODE_FLOW}[mode]
         check(self._L.tg_set_mode(self.handle, m, int(run_blocks)), "tg_set_mode")
         self._mode = mode
+
+    def set_time_limit(self, max_episode_steps):
+        """Truncate episodes at ``max_episode_steps`` steps on the device, from the next step
+        on (tg_set_time_limit); None or 0: off.  An episode already that long is truncated by
+        the next step."""
+        m = 0 if max_episode_steps is None else int(max_episode_steps)
+        check(self._L.tg_set_time_limit(self.handle, m), "tg_set_time_limit")
+        self.max_episode_steps = m or None
 
     def set_episode_capacity(self, cap):
         """Resize the completed-episode queue (discards what it holds)."""
@@ -1002,17 +1032,24 @@ class TreasureGameVectorEnv:
     episode (== ``obs`` for the others).  The reference's ``None`` reward (option could not run,
     OP/:22-23) is reward 0 with ``info["valid"] == 0``.  ``truncated`` is set only when
     ``max_episode_steps`` is given (the reference registers no TimeLimit); those envs are reset
-    by a masked ``tg_reset`` on the device, with no host synchronisation.
+    by a masked ``tg_reset`` on the device, with no host synchronisation.  With
+    ``device_time_limit=True`` the limit is the batch's own (``TreasureGameVec``'s
+    ``max_episode_steps``): the step's kernels truncate and reset, ``terminated`` / ``truncated``
+    are the done row's two bits, and ``episodes(truncated=True)`` lists truncated episodes too.
+    The step outputs are the same either way.
     Env g of ``reset(seed=s)`` is ``random.seed(s + g); TreasureGame()`` (contract of
     TreasureGameVec)."""
 
     metadata = {"autoreset_mode": "SameStep", "render_modes": ["rgb_array"]}
 
     def __init__(self, num_envs, seed=0, device=None, max_episode_steps=None, level_dir=None,
-                 mode="compact"):
+                 mode="compact", device_time_limit=False):
         self.num_envs = int(num_envs)
         self._kw = dict(device=device, level_dir=level_dir, mode=mode)
         self.max_episode_steps = None if max_episode_steps is None else int(max_episode_steps)
+        self.device_time_limit = bool(device_time_limit) and self.max_episode_steps is not None
+        if self.device_time_limit:
+            self._kw["max_episode_steps"] = self.max_episode_steps
         self.single_action_space = Discrete(_lib.NUM_ACTIONS)
         self.single_observation_space = Box(np.float32(0.0), np.float32(1.0),
                                             shape=(_lib.OBS_DIM,))
@@ -1041,6 +1078,9 @@ class TreasureGameVectorEnv:
     def step(self, actions):
         obs, rew, valid, done, info = self.env.step(actions)
         final = info["final_obs"]
+        if self.device_time_limit:
+            return (obs, rew.to(torch.float32), (done & DONE_TERMINATED).bool(),
+                    (done & DONE_TRUNCATED).bool(), {"final_obs": final, "valid": valid})
         terminated = done.bool()
         self._len += 1
         self._len.masked_fill_(terminated, 0)
@@ -1056,9 +1096,10 @@ class TreasureGameVectorEnv:
     def available_mask(self):
         return self.env.available_mask()
 
-    def episodes(self, cap=None):
-        """(env, return, length) of the terminated episodes (device queue, TreasureGameVec)"""
-        return self.env.episodes(cap)
+    def episodes(self, cap=None, truncated=False):
+        """(env, return, length) of the terminated episodes (device queue, TreasureGameVec);
+        with ``device_time_limit`` the truncated ones too (``truncated=True`` marks them)"""
+        return self.env.episodes(cap, truncated)
 
     def close(self):
         self.env.close()

@@ -64,6 +64,12 @@ extern "C" {
 /* step flags */
 #define TG_STEP_AUTORESET 1u       /* reset() an env right after a step that returned done */
 
+/* bits of a done row (tg_step, tg_rollout, tg_rollout_mlp) */
+#define TG_DONE_TERMINATED 1u      /* the env's own end (TG/:95); the only bit without a step limit */
+#define TG_DONE_TRUNCATED 2u       /* the episode reached tg_set_time_limit's limit in this step */
+/* in tg_episode.len: the episode was ended by the step limit, not by the env */
+#define TG_EPISODE_TRUNCATED (1 << 30)
+
 /* action policies of tg_policy_actions */
 #define TG_POLICY_UNIFORM 0        /* a = h(action_seed, g, t) % 9 (action_space.sample stand-in) */
 #define TG_POLICY_MASKED 1         /* k-th set bit of available_mask, k = h % popcount */
@@ -74,7 +80,8 @@ typedef struct tg_batch tg_batch;
 typedef struct {
   int64_t env;      /* global env index (global_offset + local index) */
   int32_t ret;      /* sum of step rewards since the last reset (None counts 0) */
-  int32_t len;      /* env-steps since the last reset */
+  int32_t len;      /* env-steps since the last reset, | TG_EPISODE_TRUNCATED if the step limit
+                       ended it (tg_set_time_limit) */
 } tg_episode;
 
 /* A Python-level random stream's state, as random.getstate() holds it (CPython random.py
@@ -114,6 +121,7 @@ typedef struct {
   int64_t regens_quiet; /* of regens, the generations regenerated inside k_run by its waves without
                            a chunk: the stale halves of envs whose option could not run in the step
                            that listed them (compact mode; the rest are k_regen's, or the lanes') */
+  int64_t episodes_truncated; /* of episodes, those the step limit ended (tg_set_time_limit) */
 } tg_stats;
 
 /* Create N envs on `device`: env i is `random.seed(seed_base + global_offset + i);
@@ -201,6 +209,34 @@ int tg_rollout(tg_batch *h, int32_t steps, uint64_t action_seed, int64_t t0, int
  * in meaning (timing samples group 0's kernels).  stagger != 0: group g + 1 starts after group
  * g's first k_classify.  Synchronises.  (No reference counterpart: batching is new.) */
 int tg_set_groups(tg_batch *h, int32_t groups, int32_t stagger);
+
+/* A step limit on episodes, applied on the device (the reference registers no TimeLimit; this is
+ * gymnasium's, with the same-step reset of TG_STEP_AUTORESET).  max_steps: 0 = off (the default),
+ * 1 .. 2^30 - 1; anything else is TG_E_INVAL.  Takes effect with the next step.
+ *   Scope: tg_step, tg_rollout and tg_rollout_mlp, in TG_MODE_COMPACT and TG_MODE_DIRECT, with or
+ *     without tg_set_groups.  tg_step in TG_MODE_FLOW too (it runs as compact); tg_rollout in
+ *     TG_MODE_FLOW with a limit set returns TG_E_INVAL and changes nothing (k_flow has no step
+ *     boundary to apply it at), as tg_rollout_mlp does there with or without one.  The N = 1 calls
+ *     (tg_step1*, tg_reset1*, the resident server) ignore the limit.
+ *   Length: after a step's kernels env i's episode length is len = tstep + 1 - (its episode's
+ *     start step), in uint32 arithmetic: the value tg_read_state's ep[i][1] reports.  The env is
+ *     truncated in this step iff len >= max_steps.  An env that terminated and was auto-reset in
+ *     this step has len == 0, so termination wins at len == max_steps.  (>=: lowering the limit, or
+ *     restoring ep lengths past it with tg_write_state, truncates at the next step.)
+ *   With TG_STEP_AUTORESET a truncated env, in the same call: appends {env, ret,
+ *     len | TG_EPISODE_TRUNCATED} to the episode queue (bound and dropped-record accounting as
+ *     for any record); is reset exactly as tg_reset with a mask on that env would reset it (the
+ *     same draws from its own stream: the reference's env.reset() right after that step()); has
+ *     its obs row of this step rewritten with the new episode's first observation and its done
+ *     row set to TG_DONE_TRUNCATED; final_obs, if given, already holds its pre-reset row and is
+ *     not touched; tg_read_state's ep becomes (0, 0); tg_stats.episodes and .episodes_truncated count it and
+ *     its reset's draws are added to .draws, as an auto-reset's are.
+ *   Without the flag a truncated env only gets done |= TG_DONE_TRUNCATED: no reset, no record,
+ *     and it is flagged again at every later step (gymnasium's TimeLimit).
+ *   With the limit off nothing changes: the kernels launched and their arguments are the same.
+ * A step with the limit on is bit for bit (states, MT streams, obs rows, later trajectories) the
+ * same step with the limit off followed by tg_reset(mask = the truncated envs). */
+int tg_set_time_limit(tg_batch *h, int32_t max_steps);
 
 /* available_mask for every env: u16 [N], bit k == option k can run. */
 int tg_available_mask(tg_batch *h, uint16_t *mask, void *stream);
