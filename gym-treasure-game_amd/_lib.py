@@ -50,7 +50,7 @@ EXPORTS = ("tg_create", "tg_destroy", "tg_num_envs", "tg_reset", "tg_step", "tg_
            "tg_get_stats", "tg_stats_reset", "tg_kernel_info", "tg_mt_layout", "tg_probe_dispatch", "tg_live_resources", "tg_read_state", "tg_write_state", "tg_render_init", "tg_frame_shape",
            "tg_render", "tg_frame_shape_scaled", "tg_render_scaled", "tg_frame_shape_view", "tg_render_view",
            "tg_policy_mlp_load", "tg_policy_mlp",
-           "tg_rollout_mlp", "tg_last_error", "tg_version")
+           "tg_rollout_mlp", "tg_gae", "tg_rollout_mlp_gae", "tg_last_error", "tg_version")
 
 
 class TgError(RuntimeError):
@@ -95,8 +95,8 @@ def load():
         raise TgError("libtg_amd.so is not built (%s); run __graft_entry__.build() or "
                       "python -m gym_treasure_game_amd.build" % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
-    P, i32, i64, u32, u64 = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32,
-                             ctypes.c_uint64)
+    P, i32, i64, u32, u64, f32 = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32,
+                                  ctypes.c_uint64, ctypes.c_float)
     sig = {
         "tg_create": (i32, [ctypes.POINTER(P), i64, u64, i64, i32, ctypes.c_char_p,
                             ctypes.c_char_p, ctypes.c_char_p]),
@@ -143,6 +143,9 @@ def load():
         "tg_policy_mlp_load": (i32, [P, i32, i32, i32, P, P]),
         "tg_policy_mlp": (i32, [P, u64, i64, i32, P, P, P, P, P]),
         "tg_rollout_mlp": (i32, [P, i32, u64, i64, i32, u32, P, P, P, P, P, P, P, P]),
+        "tg_gae": (i32, [P, i32, f32, f32, P, P, P, P, P, i32, P, P, P]),
+        "tg_rollout_mlp_gae": (i32, [P, i32, u64, i64, i32, u32, P, P, P, P, P, P, P, f32, f32, P, P, P,
+                                     P, P]),
         "tg_last_error": (ctypes.c_char_p, []),
         "tg_version": (ctypes.c_char_p, []),
     }

@@ -1,8 +1,8 @@
 // tg_amd.hip — MI355X (gfx950) batched Treasure Game: the host code and the C ABI of
 // include/tg_amd.h.  The kernels it launches are in the headers it includes: tg_dev.h (the device
 // layer shared with k_flow's unit, tg_flow.hip; the state layout is described there),
-// tg_kernels.h (the batch kernels), tg_timelimit.h (the step limit's kernel), tg_py1.h (the N = 1
-// path) and tg_flow.h (TG_MODE_FLOW's
+// tg_kernels.h (the batch kernels), tg_timelimit.h (the step limit's kernel), tg_value_mlp.h and
+// tg_gae_dev.h (the advantages' kernels), tg_py1.h (the N = 1 path) and tg_flow.h (TG_MODE_FLOW's
 // types; k_flow itself is instantiated by tg_flow.hip and launched through tg::flow_launch).
 #include <hip/hip_runtime.h>
 
@@ -21,9 +21,11 @@
 #include "../../include/tg_amd.h"
 #include "tg_dev.h"
 #include "tg_flow.h"
+#include "tg_gae_dev.h"
 #include "tg_kernels.h"
 #include "tg_py1.h"
 #include "tg_timelimit.h"
+#include "tg_value_mlp.h"
 
 namespace tg {
 thread_local std::string g_err;
@@ -199,9 +201,17 @@ auto step_inst(bool ar, bool fo, int policy, F f) {
 }
 // one step's kernels for a stepper's envs on `st` (io: the whole handle's arrays; the stepper's
 // rows start at c.off), their spans sampled when timing is on (the handle's own stepper, or the
-// first group)
+// first group).  vt (tg_rollout_mlp_gae; else null and nothing more is launched): the rollout's
+// vnext rows, which get the actor's value of every env the step limit resets (need_trunc_lists
+// first).
+struct TruncOut {
+  float* vnext;    // [steps][N]
+  int64_t steps;
+  int64_t row;     // this step's
+};
+int flush_trunc_list(tg_batch* h, StepCtx& c, const TruncOut& vt, hipStream_t st);
 int launch_step(tg_batch* h, StepCtx& c, const StepIO& io_in, bool ar, hipStream_t st,
-                uint32_t tstep, hipEvent_t mid = nullptr) {
+                uint32_t tstep, hipEvent_t mid = nullptr, const TruncOut* vt = nullptr) {
   StepIO io = io_in;
   io.tstep = tstep;
   if (c.off) {
@@ -252,10 +262,24 @@ int launch_step(tg_batch* h, StepCtx& c, const StepIO& io_in, bool ar, hipStream
   // the step limit (tg_set_time_limit), after everything else of the step: where a tg_reset
   // between this step and the next would stand (its block b counts in stats slot b < stat_slots)
   if (h->time_limit) {
+    if (vt && ar) {  // the states k_timelimit resets, saved while they are still there
+      const TruncList T{c.tst4.get(), c.tang.get(), c.tdst.get(), 4 * c.n};
+      const int64_t per = (int64_t)TL_TILES * TL_BLOCK;
+      hipLaunchKernelGGL(k_trunc_list, dim3((unsigned)((c.n + per - 1) / per)), dim3(TL_BLOCK), 0, st, S, c.n,
+                         h->time_limit, tstep, vt->row * h->n + c.off, T, c.tcnt.get() + c.tparity,
+                         c.tcnt.get() + (c.tparity ^ 1));
+      HIP_TRY(hipGetLastError());
+      ++c.twin;
+    }
     const auto kt = ar ? &k_timelimit<true> : &k_timelimit<false>;
     hipLaunchKernelGGL(kt, grid, block, 0, st, S, c.n, h->L, h->time_limit, tstep, io.obs, io.done, q,
                        g0, stats, err);
     HIP_TRY(hipGetLastError());
+    // An env truncates at most once in `limit` steps, so w steps append at most
+    // n * ((w - 1) / limit + 1) entries: the list's 4 n hold 4 * limit steps.  Their values, at
+    // the rollout's last step or when that bound is reached.
+    if (vt && ar && (vt->row == vt->steps - 1 || c.twin >= 4 * (int64_t)h->time_limit))
+      TG_TRY(flush_trunc_list(h, c, *vt, st));
   }
   return TG_OK;
 }
@@ -422,6 +446,79 @@ int launch_policy_mlp(tg_batch* h, int64_t off, int64_t cnt, uint64_t a0, int64_
                      cnt, h->L, h->grid.get(), M.params.get(), M.masked, mode, a0, h->g0 + off, t,
                      actions + off, logp ? logp + off : nullptr, value ? value + off : nullptr,
                      logits ? logits + off * MLP_OUT : nullptr);
+  HIP_TRY(hipGetLastError());
+  return TG_OK;
+}
+
+// k_value_mlp: envs [off, off + cnt) of the handle into value[off ..] (T.st4 null), or the list T
+// of `*count` entries, at most `bound`, into value[T.dst[k]] < total; on `st`
+int launch_value_mlp(tg_batch* h, int64_t off, int64_t cnt, const TruncList& T, const int32_t* count,
+                     int64_t bound, float* value, int64_t total, hipStream_t st) {
+  using K = decltype(&k_value_mlp<16, 0>);
+  static const K kern[4][2] = {{k_value_mlp<16, 0>, k_value_mlp<16, 1>},
+                               {k_value_mlp<32, 0>, k_value_mlp<32, 1>},
+                               {k_value_mlp<64, 0>, k_value_mlp<64, 1>},
+                               {k_value_mlp<128, 0>, k_value_mlp<128, 1>}};
+  const Mlp& M = h->mlp;
+  const int hi = M.hidden == 16 ? 0 : M.hidden == 32 ? 1 : M.hidden == 64 ? 2 : 3;
+  hipLaunchKernelGGL(kern[hi][M.act], dim3(grid_for(T.st4 ? bound : cnt)), dim3(BLOCK), 0, st,
+                     soa_of(h, off), cnt, h->L, M.params.get(), T, count, T.st4 ? value : value + off, total);
+  HIP_TRY(hipGetLastError());
+  return TG_OK;
+}
+// the values of the stepper's list into the rollout's vnext rows; the list's next use counts in
+// the other word
+int flush_trunc_list(tg_batch* h, StepCtx& c, const TruncOut& vt, hipStream_t st) {
+  if (!c.twin) return TG_OK;
+  const TruncList T{c.tst4.get(), c.tang.get(), c.tdst.get(), 4 * c.n};
+  int64_t bound = c.n * ((c.twin - 1) / (int64_t)h->time_limit + 1);
+  if (bound > T.cap) bound = T.cap;
+  TG_TRY(launch_value_mlp(h, 0, 0, T, c.tcnt.get() + c.tparity, bound, vt.vnext, vt.steps * h->n, st));
+  c.tparity ^= 1;
+  c.twin = 0;
+  return TG_OK;
+}
+// a stepper's list of truncated envs and its two count words (zero between uses: k_trunc_list),
+// at first use; the zeroing is queued on `st`, the stream the stepper's kernels follow on.  The
+// count is an int32 over at most 4 n entries, so a stepper of more than 2^28 envs is refused.
+// A call that failed after a k_trunc_list and before the value kernel left entries behind
+// (twin != 0): the count words are zeroed again, so none of them reaches this call's rows.
+int need_trunc_lists(StepCtx& c, hipStream_t st) {
+  if (c.n > ((int64_t)1 << 28))
+    return fail(TG_E_INVAL, "tg_rollout_mlp_gae: more than 2^28 envs in one stepper (%lld) with a step "
+                            "limit and TG_STEP_AUTORESET", (long long)c.n);
+  if (c.tst4 && c.tang && c.tdst && c.tcnt) {
+    if (c.twin) {
+      HIP_TRY(hipMemsetAsync(c.tcnt.get(), 0, 2 * sizeof(int32_t), st));
+      c.tparity = 0;
+      c.twin = 0;
+    }
+    return TG_OK;
+  }
+  int rc = c.tst4.alloc(4 * (size_t)c.n, "the truncated envs' states");
+  if (!rc) rc = c.tang.alloc(4 * (size_t)c.n, "the truncated envs' angles");
+  if (!rc) rc = c.tdst.alloc(4 * (size_t)c.n, "the truncated envs' destinations");
+  if (!rc) rc = c.tcnt.alloc(2, "the truncated envs' count");
+  if (!rc && hipMemsetAsync(c.tcnt.get(), 0, 2 * sizeof(int32_t), st) != hipSuccess)
+    rc = fail(TG_E_HIP, "hipMemsetAsync: the truncated envs' count");
+  if (rc) {  // all or nothing: a failed call holds no more than the handle held before it
+    c.tst4.reset();
+    c.tang.reset();
+    c.tdst.reset();
+    c.tcnt.reset();
+    return rc;
+  }
+  c.tparity = 0;
+  c.twin = 0;
+  return TG_OK;
+}
+// k_gae over the handle's n envs on `st`
+int launch_gae(tg_batch* h, int32_t steps, float gamma, float lambda, const int32_t* reward,
+               const uint8_t* done, const float* value, float* vnext, const float* vboot,
+               int vnext_given, float* adv, float* ret, hipStream_t st) {
+  const auto kern = vnext ? &k_gae<true> : &k_gae<false>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)((h->n + GAE_BLOCK - 1) / GAE_BLOCK)), dim3(GAE_BLOCK), 0, st,
+                     steps, h->n, gamma, lambda, reward, done, value, vnext, vboot, vnext_given, adv, ret);
   HIP_TRY(hipGetLastError());
   return TG_OK;
 }
@@ -1082,21 +1179,33 @@ int tg_policy_mlp(tg_batch* h, uint64_t a0, int64_t t, int32_t mode, int32_t* ac
                            (hipStream_t)stream);
 }
 
-int tg_rollout_mlp(tg_batch* h, int32_t steps, uint64_t a0, int64_t t0, int32_t mode, uint32_t flags,
-                   int32_t* actions, double* obs, int32_t* reward, uint8_t* valid, uint8_t* done,
-                   float* logp, float* value, void* stream) {
-  BIND(h);
-  if (!h->mlp.hidden) return fail(TG_E_STATE, "tg_rollout_mlp: no parameters (tg_policy_mlp_load)");
+}  // extern "C"
+
+namespace {
+// tg_rollout_mlp (vnext null) and tg_rollout_mlp_gae's rollout (`who`): with vnext, a limit and
+// auto-reset, row s of vnext gets the value of every env the limit resets in step s
+int rollout_mlp(tg_batch* h, const char* who, int32_t steps, uint64_t a0, int64_t t0, int32_t mode,
+                uint32_t flags, int32_t* actions, double* obs, int32_t* reward, uint8_t* valid,
+                uint8_t* done, float* logp, float* value, float* vnext, bool own_vboot, void* stream) {
+  if (!h->mlp.hidden) return fail(TG_E_STATE, "%s: no parameters (tg_policy_mlp_load)", who);
   if (h->mode == TG_MODE_FLOW)
-    return fail(TG_E_INVAL, "tg_rollout_mlp: TG_MODE_FLOW evaluates its policy inside k_flow; use "
-                            "TG_MODE_COMPACT or TG_MODE_DIRECT");
+    return fail(TG_E_INVAL, "%s: TG_MODE_FLOW evaluates its policy inside k_flow; use "
+                            "TG_MODE_COMPACT or TG_MODE_DIRECT", who);
   if (steps == 0) return TG_OK;
-  TG_TRY(rollout_prep(h, "tg_rollout_mlp", steps, mode == TG_MLP_SAMPLE || mode == TG_MLP_GREEDY, obs,
+  TG_TRY(rollout_prep(h, who, steps, mode == TG_MLP_SAMPLE || mode == TG_MLP_GREEDY, obs,
                       reward, valid, done));
   const int64_t n = h->n;
   if (!actions && !h->mlp.actions)  // the step kernels always read an action row
     TG_TRY(h->mlp.actions.alloc((size_t)n, "tg_rollout_mlp's action scratch"));
+  if (own_vboot && !h->mlp.vboot) TG_TRY(h->mlp.vboot.alloc((size_t)n, "tg_rollout_mlp_gae's vboot scratch"));
   const bool ar = (flags & TG_STEP_AUTORESET) != 0;
+  if (vnext && ar && h->time_limit) {  // every stepper run_steps will use
+    if (h->grp.empty() || h->mode != TG_MODE_COMPACT) {
+      TG_TRY(need_trunc_lists(h->main, (hipStream_t)stream));
+    } else {
+      for (auto& c : h->grp) TG_TRY(need_trunc_lists(c, c.st.get()));
+    }
+  }
   const uint32_t tb = h->tstep;
   h->tstep += (uint32_t)steps;
   // step s of a stepper: the actor into row s, then the step kernels with those actions given
@@ -1109,8 +1218,57 @@ int tg_rollout_mlp(tg_batch* h, int32_t steps, uint64_t a0, int64_t t0, int32_t 
     if (rc) return rc;
     const StepIO io{act, obs ? obs + (size_t)s * n * 9 : h->obs_scratch.get(), reward + (size_t)s * n,
                     valid + (size_t)s * n, done + (size_t)s * n, nullptr, -1, 0, 0};
-    return launch_step(h, c, io, ar, st, tb + (uint32_t)s, mid);
+    const TruncOut vt{vnext, steps, s};
+    return launch_step(h, c, io, ar, st, tb + (uint32_t)s, mid, vnext ? &vt : nullptr);
   });
+}
+}  // namespace
+
+extern "C" {
+
+int tg_rollout_mlp(tg_batch* h, int32_t steps, uint64_t a0, int64_t t0, int32_t mode, uint32_t flags,
+                   int32_t* actions, double* obs, int32_t* reward, uint8_t* valid, uint8_t* done,
+                   float* logp, float* value, void* stream) {
+  BIND(h);
+  return rollout_mlp(h, "tg_rollout_mlp", steps, a0, t0, mode, flags, actions, obs, reward, valid, done,
+                     logp, value, nullptr, false, stream);
+}
+
+// ---- advantages (tg_gae.h) -------------------------------------------------------------------
+int tg_gae(tg_batch* h, int32_t steps, float gamma, float lambda, const int32_t* reward,
+           const uint8_t* done, const float* value, float* vnext, const float* vboot,
+           int32_t vnext_given, float* adv, float* ret, void* stream) {
+  BIND(h);
+  if (!gae_coeff_ok(gamma) || !gae_coeff_ok(lambda))
+    return fail(TG_E_INVAL, "tg_gae: gamma %g and lambda %g must lie in [0, 1]", (double)gamma, (double)lambda);
+  if (steps == 0) return TG_OK;  // (rows of no steps have no address)
+  if (steps < 0 || !reward || !done || !value || !vboot || !adv || !ret || (vnext_given && !vnext))
+    return fail(TG_E_INVAL, "tg_gae: bad arguments");
+  return launch_gae(h, steps, gamma, lambda, reward, done, value, vnext, vboot, vnext_given ? 1 : 0, adv,
+                    ret, (hipStream_t)stream);
+}
+
+int tg_rollout_mlp_gae(tg_batch* h, int32_t steps, uint64_t a0, int64_t t0, int32_t mode, uint32_t flags,
+                       int32_t* actions, double* obs, int32_t* reward, uint8_t* valid, uint8_t* done,
+                       float* logp, float* value, float gamma, float lambda, float* adv, float* ret,
+                       float* vnext, float* vboot, void* stream) {
+  BIND(h);
+  if (!gae_coeff_ok(gamma) || !gae_coeff_ok(lambda))
+    return fail(TG_E_INVAL, "tg_rollout_mlp_gae: gamma %g and lambda %g must lie in [0, 1]", (double)gamma,
+                (double)lambda);
+  if (!adv || !ret || !value) return fail(TG_E_INVAL, "tg_rollout_mlp_gae: adv, ret and value are required");
+  const bool parks = h->time_limit && (flags & TG_STEP_AUTORESET);  // the truncated values, in vnext
+  if (parks && !vnext)
+    return fail(TG_E_INVAL, "tg_rollout_mlp_gae: with a step limit and TG_STEP_AUTORESET vnext is required "
+                            "(the truncated envs' values are parked there)");
+  TG_TRY(rollout_mlp(h, "tg_rollout_mlp_gae", steps, a0, t0, mode, flags, actions, obs, reward, valid, done,
+                     logp, value, vnext, !vboot, stream));
+  if (steps == 0) return TG_OK;
+  // (with groups, the caller's stream has joined them: run_steps)
+  float* const vb = vboot ? vboot : h->mlp.vboot.get();
+  TG_TRY(launch_value_mlp(h, 0, h->n, TruncList{}, nullptr, 0, vb, h->n, (hipStream_t)stream));
+  return launch_gae(h, steps, gamma, lambda, reward, done, value, vnext, vb, parks ? 1 : 0, adv, ret,
+                    (hipStream_t)stream);
 }
 
 // ---- state in and out ------------------------------------------------------------------------

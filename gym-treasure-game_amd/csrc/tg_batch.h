@@ -212,6 +212,14 @@ struct StepCtx {
   DevBuf<int32_t> regen_ctr;  // per XCD: k_regen's grab counters and the lists' lengths, two
                               // sets (k_regen zeroes the other set for the next launch)
   int regen_parity = 0;       // which set the next k_regen counts in
+  // tg_rollout_mlp_gae: the saved states of the envs k_timelimit is about to reset (k_trunc_list;
+  // allocated at first use): 4 n entries, which bounds what 4 x limit steps can append
+  DevBuf<uint4> tst4;
+  DevBuf<double2> tang;
+  DevBuf<int64_t> tdst;
+  DevBuf<int32_t> tcnt;       // the list's length, two words: one per use of the list, in turn
+  int tparity = 0;            // which word of tcnt the list counts in now
+  int64_t twin = 0;           // steps appended since k_value_mlp last ran over the list
   Stream st;                  // a group's stream (groups only)
   Event ev;                   //   and its join event
 };
@@ -240,6 +248,7 @@ struct Mlp {
   DevBuf<float> params;
   int hidden = 0, act = 0, masked = 0;
   DevBuf<int32_t> actions;  // tg_rollout_mlp without an actions output
+  DevBuf<float> vboot;      // tg_rollout_mlp_gae without a vboot output
 };
 
 // TG_MODE_FLOW's work structures (tg_flow.h Flow; allocated at the first flow rollout)

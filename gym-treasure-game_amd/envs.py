@@ -288,7 +288,7 @@ class TreasureGameVec:
                 self._out(self._done), info)
 
     def rollout(self, steps, t0=0, action_seed=0x5EED0001, policy="uniform", obs=True,
-                actions=True, check_flow=True):
+                actions=True, check_flow=True, gae=None):
         """``steps`` env-steps in one call with the on-device synthetic policy (tg_rollout):
         step t0 + s takes ``policy_actions(t0 + s, action_seed, policy)``, evaluated inside the
         step kernels.  Returns step-major device tensors: reward i32 [K, N], valid / done u8
@@ -298,6 +298,12 @@ class TreasureGameVec:
         ``policy="mlp"`` / ``"mlp_greedy"``: the learned actor of ``set_policy_mlp`` instead
         (tg_rollout_mlp: per step the actor kernel, then the step kernels), which also returns
         "logp" and "value" f32 [K, N]; not in "flow" mode.
+
+        ``gae=(gamma, lam)`` with one of the mlp policies (tg_rollout_mlp_gae): also "adv", "ret"
+        and "vnext" f32 [K, N] and "vboot" f32 [N], the advantages of include/tg_amd.h's
+        definition with the actor's value of every env after the last step as the bootstrap
+        and, with auto-reset and a step limit, of every truncated env's pre-reset state.  The
+        other outputs and the state the call leaves are unchanged by it.
 
         In "flow" mode a k_flow launch that fails its protocol checks (a wait past its bound,
         a sub-problem left unstepped, an item out of range) sets TG_ERR_FLOW and its rows are
@@ -314,6 +320,9 @@ class TreasureGameVec:
             out["obs"] = torch.empty((k, n, 9), dtype=torch.float64, device=dev)
         if actions:
             out["actions"] = torch.empty((k, n), dtype=torch.int32, device=dev)
+        if gae is not None and policy not in ("mlp", "mlp_greedy"):
+            raise TgError("rollout(gae=...) needs policy='mlp' or 'mlp_greedy' (the advantages use "
+                          "the learned actor's value); gae() takes any rollout's rows")
         if policy in ("mlp", "mlp_greedy"):
             # the learned actor (set_policy_mlp) as the policy: also "logp" and "value" f32 [K, N];
             # the row the policy saw at step s is obs[s - 1] (observe() before the call for s = 0)
@@ -322,9 +331,22 @@ class TreasureGameVec:
                               "evaluates its policy inside the kernel)" % policy)
             out["logp"] = torch.empty((k, n), dtype=torch.float32, device=dev)
             out["value"] = torch.empty((k, n), dtype=torch.float32, device=dev)
+            mlp_mode = _lib.TG_MLP_GREEDY if policy == "mlp_greedy" else _lib.TG_MLP_SAMPLE
+            if gae is not None:
+                gamma, lam = gae
+                for key in ("adv", "ret", "vnext"):
+                    out[key] = torch.empty((k, n), dtype=torch.float32, device=dev)
+                out["vboot"] = torch.empty(n, dtype=torch.float32, device=dev)
+                check(self._L.tg_rollout_mlp_gae(
+                    self.handle, k, action_seed, int(t0), mlp_mode,
+                    _lib.TG_STEP_AUTORESET if self.autoreset else 0, _ptr(out.get("actions")),
+                    _ptr(out.get("obs")), _ptr(out["reward"]), _ptr(out["valid"]),
+                    _ptr(out["done"]), _ptr(out["logp"]), _ptr(out["value"]), float(gamma),
+                    float(lam), _ptr(out["adv"]), _ptr(out["ret"]), _ptr(out["vnext"]),
+                    _ptr(out["vboot"]), self._stream()), "tg_rollout_mlp_gae")
+                return out
             check(self._L.tg_rollout_mlp(
-                self.handle, k, action_seed, int(t0),
-                _lib.TG_MLP_GREEDY if policy == "mlp_greedy" else _lib.TG_MLP_SAMPLE,
+                self.handle, k, action_seed, int(t0), mlp_mode,
                 _lib.TG_STEP_AUTORESET if self.autoreset else 0, _ptr(out.get("actions")),
                 _ptr(out.get("obs")), _ptr(out["reward"]), _ptr(out["valid"]), _ptr(out["done"]),
                 _ptr(out["logp"]), _ptr(out["value"]), self._stream()), "tg_rollout_mlp")
@@ -337,6 +359,38 @@ class TreasureGameVec:
                                  self._stream()), "tg_rollout")
         if check_flow and self._mode == "flow" and self.errors() & _lib.TG_ERR_FLOW:
             raise TgError("tg_rollout: a k_flow launch set TG_ERR_FLOW (its rows are not valid)")
+        return out
+
+    def gae(self, reward, done, value, vboot, gamma, lam, vnext=None):
+        """Advantages of any rollout's step-major rows (tg_gae; the definition:
+        include/tg_amd.h): ``reward`` i32, ``done`` u8, ``value`` f32 [K, N] and ``vboot`` f32
+        [N] (the value of every env's state after the last step), contiguous tensors on the
+        env's device.  ``vnext`` f32 [K, N]: its entries where ``done`` is DONE_TRUNCATED alone
+        are read as the value of the truncated env's pre-reset state (a step() loop gets them
+        from ``final_obs``); None: a truncated env's next value is ``value[s + 1]`` (``vboot``
+        after the last step).  Returns ``{"adv", "ret", "vnext"}`` f32 [K, N]; a given
+        ``vnext`` is completed in place."""
+        n, dev = self.num_envs, self.device
+        if not (isinstance(reward, torch.Tensor) and reward.dim() == 2 and reward.shape[1] == n):
+            raise ValueError("reward must be a [K, num_envs] tensor")
+        k = int(reward.shape[0])
+        want = {"reward": (reward, (k, n), torch.int32), "done": (done, (k, n), torch.uint8),
+                "value": (value, (k, n), torch.float32), "vboot": (vboot, (n,), torch.float32)}
+        if vnext is not None:
+            want["vnext"] = (vnext, (k, n), torch.float32)
+        for name, (t, shape, dt) in want.items():
+            if not (isinstance(t, torch.Tensor) and t.dtype == dt and tuple(t.shape) == shape
+                    and t.is_contiguous() and t.device == dev):
+                raise ValueError("%s must be a contiguous %s tensor of shape %s on %s"
+                                 % (name, dt, shape, dev))
+        out = {"adv": torch.empty((k, n), dtype=torch.float32, device=dev),
+               "ret": torch.empty((k, n), dtype=torch.float32, device=dev),
+               "vnext": vnext if vnext is not None
+               else torch.empty((k, n), dtype=torch.float32, device=dev)}
+        check(self._L.tg_gae(self.handle, k, float(gamma), float(lam), _ptr(reward), _ptr(done),
+                             _ptr(value), _ptr(out["vnext"]), _ptr(vboot),
+                             0 if vnext is None else 1, _ptr(out["adv"]), _ptr(out["ret"]),
+                             self._stream()), "tg_gae")
         return out
 
     def set_groups(self, groups=1, stagger=False):

@@ -511,6 +511,61 @@ int tg_rollout_mlp(tg_batch *h, int32_t steps, uint64_t action_seed, int64_t t0,
                    uint32_t flags, int32_t *actions, double *obs, int32_t *reward, uint8_t *valid,
                    uint8_t *done, float *logp, float *value, void *stream);
 
+/* ---- advantages on the device (an extension: the reference has no learner) -----------------
+ * Generalised advantage estimation over a rollout's step-major rows, one env per column.  All
+ * f32, every multiply-add an explicit fmaf, so a column's results depend on that column alone
+ * (not on batch size, sharding, groups or tiling) and are reproducible bit for bit on a CPU.
+ * For env i the scan runs s = K-1 .. 0 from A_K = 0, with gl = gamma * lambda (one f32 product):
+ *   term  = done[s][i] & TG_DONE_TERMINATED;  trunc = done[s][i] & TG_DONE_TRUNCATED
+ *   nv    = term ? 0
+ *         : trunc && the env was reset in this step ? vtrunc[s][i]   (V of the pre-reset state)
+ *         : s == K-1 ? vboot[i] : value[s+1][i]
+ *   delta = fmaf(gamma, nv, (float)reward[s][i]) - value[s][i]
+ *   carry = done[s][i] != 0 ? 0 : A_{s+1}
+ *   A_s   = fmaf(gl, carry, delta)
+ *   adv[s][i] = A_s;  ret[s][i] = A_s + value[s][i];  vnext[s][i] = nv
+ * "Reset in this step": the rollout ran with TG_STEP_AUTORESET and a step limit.  Without the flag
+ * a truncated env is not reset (tg_set_time_limit): its next state is the one value[s+1] or vboot
+ * saw, so those are used and only the recursion is cut.  With auto-reset the two bits never
+ * coincide (termination wins at len == max_steps); where both are set, term wins.  A step with
+ * valid == 0 is an ordinary transition with reward 0; the caller masks it if it wants to.
+ * vnext, "the value of the state each step led to, 0 after termination", is written in full (TD
+ * targets); it is also where the truncated envs' values are handed in.
+ *
+ * tg_gae: the scan alone over caller-owned DEVICE rows of any rollout (a tg_step loop's too):
+ * reward int32, done u8, value f32 [K][N], vboot f32 [N] in; adv, ret f32 [K][N] out.
+ * vnext_given 1: vnext's entries whose done has TG_DONE_TRUNCATED set and TG_DONE_TERMINATED clear
+ * are read as vtrunc before they are rewritten; 0: nothing is read from vnext, which may then be
+ * NULL (not stored).  One kernel on `stream`, no synchronisation.  TG_E_INVAL, with nothing
+ * launched: gamma or lambda outside [0, 1] or not finite, steps < 0, a null reward, done, value,
+ * vboot, adv or ret, vnext_given with a null vnext.  steps == 0: TG_OK. */
+int tg_gae(tg_batch *h, int32_t steps, float gamma, float lambda, const int32_t *reward,
+           const uint8_t *done, const float *value, float *vnext, const float *vboot,
+           int32_t vnext_given, float *adv, float *ret, void *stream);
+/* tg_rollout_mlp, then vboot = the actor's value of every env after step K, then tg_gae.
+ * Everything tg_rollout_mlp writes, and the state it leaves (MT streams, episode queue, stats),
+ * is bit for bit what it is without the advantages; value is required here.  With a step limit
+ * and TG_STEP_AUTORESET, each step also saves the state words of the envs the limit is about to
+ * reset, before they are reset (one small kernel per step into a device-side list), and a
+ * value-only actor kernel runs over the list after the last step (earlier when the list's bound
+ * is reached), so the cost follows the number of truncated envs.  The values go to vnext[s][i]
+ * and the scan reads those (vnext_given = 1); each is tg_policy_mlp's value of that state.
+ * Otherwise vnext_given = 0.
+ * vboot f32 [N] (NULL: a scratch the handle owns) is tg_policy_mlp's value row after the call.
+ * With tg_set_groups the per-step kernels run on the groups' streams with lists of their own;
+ * vboot and the scan follow on the caller's stream after the join.  No synchronisation (the
+ * lists and the scratch are allocated at first use).
+ * TG_E_INVAL, with nothing changed (the step count included): gamma or lambda outside [0, 1] or
+ * not finite; a null adv, ret or value; a null vnext while a limit is set and TG_STEP_AUTORESET is
+ * given (with no limit vnext may be NULL: not stored); TG_MODE_FLOW; more than 2^28 envs in the
+ * handle (or in a group) with a limit and TG_STEP_AUTORESET (the list's count is an int32 over
+ * 4 entries per env); whatever tg_rollout_mlp rejects.  steps == 0: TG_OK. */
+int tg_rollout_mlp_gae(tg_batch *h, int32_t steps, uint64_t action_seed, int64_t t0, int32_t mode,
+                       uint32_t flags, int32_t *actions, double *obs, int32_t *reward,
+                       uint8_t *valid, uint8_t *done, float *logp, float *value, float gamma,
+                       float lambda, float *adv, float *ret, float *vnext, float *vboot,
+                       void *stream);
+
 const char *tg_last_error(void);
 const char *tg_version(void);
 
