@@ -8,9 +8,9 @@ The step path runs in libtg_amd.so (hand-written HIP for gfx950, C ABI in includ
 there is no CPU fallback.  Registration with gym / gymnasium happens on import when either is
 installed, mirroring gym_treasure_game/__init__.py:3-6.
 """
-from ._lib import TG_ERR_FLOW, TgError  # noqa: F401
+from ._lib import TG_EPISODE_TRUNCATED, TG_ERR_FLOW, TG_ERR_INDEX, TgError  # noqa: F401
 from .envs import (DONE_TERMINATED, DONE_TRUNCATED, OPTION_NAMES, STATE_NAMES,  # noqa: F401
-                   GpuOption, ObservationWrapper,
+                   GpuOption, ObservationWrapper, Snapshot,
                    TreasureGame, TreasureGameVec, TreasureGameVectorEnv, make_vec,
                    mlp_param_count, pack_mlp_params, read_level)
 from .render import load_sprites, synthetic_sprites  # noqa: F401

@@ -28,6 +28,7 @@ TG_ERR_NEARINT = 1 << 27
 TG_ERR_RENDER = 1 << 28
 TG_ERR_WINDOW = 1 << 29
 TG_ERR_FLOW = 1 << 30
+TG_ERR_INDEX = 1 << 31
 TG_SPR_COUNT = 24
 TG_FRAME_RGB = 3
 TG_FRAME_GRAY = 1
@@ -47,7 +48,9 @@ EXPORTS = ("tg_create", "tg_destroy", "tg_num_envs", "tg_reset", "tg_step", "tg_
            "tg_available_mask",
            "tg_observe", "tg_policy_actions", "tg_episodes", "tg_errors", "tg_set_mode", "tg_set_timing", "tg_regenerate",
            "tg_set_episode_capacity", "tg_set_time_limit", "tg_predicate_table",
-           "tg_get_stats", "tg_stats_reset", "tg_kernel_info", "tg_mt_layout", "tg_probe_dispatch", "tg_live_resources", "tg_read_state", "tg_write_state", "tg_render_init", "tg_frame_shape",
+           "tg_get_stats", "tg_stats_reset", "tg_kernel_info", "tg_mt_layout", "tg_probe_dispatch", "tg_live_resources", "tg_read_state", "tg_write_state",
+           "tg_snap_create", "tg_snap_destroy", "tg_snap_slots", "tg_snap_save", "tg_snap_load", "tg_snap_read",
+           "tg_snap_write", "tg_render_init", "tg_frame_shape",
            "tg_render", "tg_frame_shape_scaled", "tg_render_scaled", "tg_frame_shape_view", "tg_render_view",
            "tg_policy_mlp_load", "tg_policy_mlp",
            "tg_rollout_mlp", "tg_gae", "tg_rollout_mlp_gae", "tg_last_error", "tg_version")
@@ -133,6 +136,13 @@ def load():
                                  ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
         "tg_read_state": (i32, [P, P, P, P, P, P, P, P]),
         "tg_write_state": (i32, [P, P, P, P, P, P, P, P]),
+        "tg_snap_create": (i32, [P, i64, ctypes.POINTER(P)]),
+        "tg_snap_destroy": (None, [P]),
+        "tg_snap_slots": (i64, [P]),
+        "tg_snap_save": (i32, [P, P, P, P, i64, P]),
+        "tg_snap_load": (i32, [P, P, P, P, P, i64, P]),
+        "tg_snap_read": (i32, [P, i64, i64, P, P, P, P, P, P, P]),
+        "tg_snap_write": (i32, [P, i64, i64, P, P, P, P, P, P, P]),
         "tg_render_init": (i32, [P, P, i32, i32]),
         "tg_frame_shape": (i32, [P, ctypes.POINTER(i32), ctypes.POINTER(i32)]),
         "tg_render": (i32, [P, i64, i64, P, P]),

@@ -24,6 +24,7 @@
 #include "tg_gae_dev.h"
 #include "tg_kernels.h"
 #include "tg_py1.h"
+#include "tg_snap_kernels.h"
 #include "tg_timelimit.h"
 #include "tg_value_mlp.h"
 
@@ -1399,6 +1400,161 @@ int tg_write_state(tg_batch* h, const int32_t* pos, const uint32_t* flags, const
   hipLaunchKernelGGL(k_gen_twist, dim3(grid_for(n)), dim3(BLOCK), 0, 0, h->S, n, 0u, 1,
                      2 * MT_HALF_GENS - 1);
   HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  return TG_OK;
+}
+
+// ---- snapshots ---------------------------------------------------------------------------------
+int tg_snap_create(tg_batch* h, int64_t slots, tg_snap** out) {
+  BIND(h);
+  if (!out || slots <= 0) return fail(TG_E_INVAL, "tg_snap_create: slots %lld, or a null output", (long long)slots);
+  *out = nullptr;
+  auto s = std::make_unique<tg_snap>();
+  s->owner = h;
+  s->slots = slots;
+  TG_TRY(s->st4.alloc((size_t)slots, "snapshot states"));
+  TG_TRY(s->ang.alloc((size_t)slots, "snapshot angles"));
+  TG_TRY(s->ep.alloc((size_t)slots, "snapshot episodes"));
+  TG_TRY(s->mt.alloc(MT_N * (size_t)slots, "snapshot generations"));
+  HIP_TRY(hipMemset(s->st4.get(), 0, sizeof(uint4) * (size_t)slots));
+  HIP_TRY(hipMemset(s->ang.get(), 0, sizeof(double2) * (size_t)slots));
+  HIP_TRY(hipMemset(s->ep.get(), 0, sizeof(int2) * (size_t)slots));
+  HIP_TRY(hipMemset(s->mt.get(), 0, sizeof(uint32_t) * MT_N * (size_t)slots));
+  HIP_TRY(hipDeviceSynchronize());
+  *out = s.get();
+  h->snaps.push_back(std::move(s));
+  return TG_OK;
+}
+
+void tg_snap_destroy(tg_snap* s) {
+  if (!s || !s->owner) return;
+  tg_batch* const h = s->owner;
+  int cur = -1;
+  if (hipGetDevice(&cur) == hipSuccess && cur != h->device) (void)hipSetDevice(h->device);
+  (void)hipDeviceSynchronize();  // no queued save or load runs against a freed slot
+  for (auto it = h->snaps.begin(); it != h->snaps.end(); ++it)
+    if (it->get() == s) {
+      h->snaps.erase(it);  // its buffers: by their owners
+      return;
+    }
+}
+
+int64_t tg_snap_slots(const tg_snap* s) { return s ? s->slots : 0; }
+
+namespace {
+Snap snap_view(const tg_snap* s) { return Snap{s->st4.get(), s->ang.get(), s->ep.get(), s->mt.get()}; }
+int snap_args(const char* who, const tg_batch* h, const tg_snap* s, const int64_t* envs,
+              const int64_t* slots, int64_t count) {
+  if (!s || !envs || !slots) return fail(TG_E_INVAL, "%s: a null snapshot, envs or slots", who);
+  if (s->owner != h) return fail(TG_E_INVAL, "%s: the snapshot belongs to another handle", who);
+  if (count < 0) return fail(TG_E_INVAL, "%s: count %lld < 0", who, (long long)count);
+  if (count > (int64_t)1 << 31)  // (the launches' grids)
+    return fail(TG_E_INVAL, "%s: count %lld > 2^31", who, (long long)count);
+  return TG_OK;
+}
+int snap_range(const char* who, const tg_snap* s, int64_t first, int64_t count) {
+  if (!s) return fail(TG_E_INVAL, "%s: null snapshot", who);
+  if (first < 0 || count < 0 || first > s->slots || count > s->slots - first)
+    return fail(TG_E_INVAL, "%s: slots [%lld, +%lld) of %lld", who, (long long)first, (long long)count,
+                (long long)s->slots);
+  return TG_OK;
+}
+}  // namespace
+
+int tg_snap_save(tg_batch* h, tg_snap* s, const int64_t* envs, const int64_t* slots, int64_t count,
+                 void* stream) {
+  BIND(h);
+  TG_TRY(snap_args("tg_snap_save", h, s, envs, slots, count));
+  if (count == 0) return TG_OK;
+  const int64_t threads = count * SNAP_Q;
+  hipLaunchKernelGGL(k_snap_save, dim3((unsigned)((threads + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0,
+                     (hipStream_t)stream, h->S, h->n, snap_view(s), s->slots, envs, slots, count,
+                     h->tstep, h->err.get());
+  HIP_TRY(hipGetLastError());
+  return TG_OK;
+}
+
+int tg_snap_load(tg_batch* h, const tg_snap* s, const int64_t* slots, const int64_t* envs,
+                 const uint64_t* seeds, int64_t count, void* stream) {
+  BIND(h);
+  TG_TRY(snap_args("tg_snap_load", h, s, envs, slots, count));
+  if (count == 0) return TG_OK;
+  constexpr int WAVES = BLOCK / 64;  // one wavefront per entry
+  const dim3 grid((unsigned)((count + WAVES - 1) / WAVES));
+  hipStream_t st = (hipStream_t)stream;
+  if (seeds) {
+    hipLaunchKernelGGL(k_snap_seed, dim3(grid_for(count)), dim3(BLOCK), 0, st, h->S, h->n, s->slots,
+                       envs, slots, seeds, count, h->genrand.get());
+    hipLaunchKernelGGL(k_snap_load<true>, grid, dim3(BLOCK), 0, st, h->S, h->n, snap_view(s), s->slots,
+                       slots, envs, count, h->tstep, h->err.get());
+  } else {
+    hipLaunchKernelGGL(k_snap_load<false>, grid, dim3(BLOCK), 0, st, h->S, h->n, snap_view(s), s->slots,
+                       slots, envs, count, h->tstep, h->err.get());
+  }
+  HIP_TRY(hipGetLastError());
+  return TG_OK;
+}
+
+int tg_snap_read(tg_snap* s, int64_t first, int64_t count, int32_t* pos, uint32_t* flags,
+                 int32_t* objs, double* ang, uint32_t* mt, uint32_t* mt_pos, int32_t* ep) {
+  TG_TRY(snap_range("tg_snap_read", s, first, count));
+  BIND(s->owner);
+  HIP_TRY(hipDeviceSynchronize());
+  if (count == 0) return TG_OK;
+  if (pos || flags || objs || mt_pos) {
+    std::vector<uint4> st((size_t)count);
+    HIP_TRY(hipMemcpy(st.data(), s->st4.get() + first, sizeof(uint4) * count, hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < count; ++i) {
+      Env e;
+      unpack_st4(st[(size_t)i], e);
+      if (pos) pos[2 * i] = e.px, pos[2 * i + 1] = e.py;
+      if (flags) flags[i] = e.f;
+      if (objs) objs[4 * i] = e.kx, objs[4 * i + 1] = e.ky, objs[4 * i + 2] = e.gx, objs[4 * i + 3] = e.gy;
+      if (mt_pos) mt_pos[i] = e.mti;
+    }
+  }
+  if (ang) HIP_TRY(hipMemcpy(ang, s->ang.get() + first, sizeof(double2) * count, hipMemcpyDeviceToHost));
+  if (ep) HIP_TRY(hipMemcpy(ep, s->ep.get() + first, sizeof(int2) * count, hipMemcpyDeviceToHost));
+  if (mt)
+    HIP_TRY(hipMemcpy(mt, s->mt.get() + first * MT_N, sizeof(uint32_t) * MT_N * (size_t)count,
+                      hipMemcpyDeviceToHost));
+  return TG_OK;
+}
+
+int tg_snap_write(tg_snap* s, int64_t first, int64_t count, const int32_t* pos, const uint32_t* flags,
+                  const int32_t* objs, const double* ang, const uint32_t* mt, const uint32_t* mt_pos,
+                  const int32_t* ep) {
+  TG_TRY(snap_range("tg_snap_write", s, first, count));
+  BIND(s->owner);
+  if (!pos || !flags || !objs || !ang || !mt || !mt_pos)
+    return fail(TG_E_INVAL, "tg_snap_write: pos, flags, objs, ang, mt and mt_pos are required");
+  std::vector<uint4> st((size_t)count);
+  for (int64_t i = 0; i < count; ++i) {
+    const uint32_t p = mt_pos[i];
+    if (p > (uint32_t)MT_N || (p & 1u))
+      return fail(TG_E_INVAL, "tg_snap_write: record %lld: mt_pos %u (must be even, <= 624: "
+                  "random() consumes words in pairs)", (long long)i, p);
+    for (int k = 0; k < 2; ++k)
+      if (pos[2 * i + k] < -32768 || pos[2 * i + k] > 32767)
+        return fail(TG_E_INVAL, "tg_snap_write: record %lld: position out of range", (long long)i);
+    for (int k = 0; k < 4; ++k)
+      if (objs[4 * i + k] < -128 || objs[4 * i + k] > 127)
+        return fail(TG_E_INVAL, "tg_snap_write: record %lld: object cell out of range", (long long)i);
+    Env e{};
+    e.px = pos[2 * i], e.py = pos[2 * i + 1];
+    e.f = flags[i];
+    e.kx = objs[4 * i], e.ky = objs[4 * i + 1], e.gx = objs[4 * i + 2], e.gy = objs[4 * i + 3];
+    e.mti = p;  // stored as given: tg_snap_load gives 624 tg_write_state's meaning
+    st[(size_t)i] = pack(e);
+  }
+  HIP_TRY(hipDeviceSynchronize());
+  if (count == 0) return TG_OK;
+  HIP_TRY(hipMemcpy(s->st4.get() + first, st.data(), sizeof(uint4) * count, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(s->ang.get() + first, ang, sizeof(double2) * count, hipMemcpyHostToDevice));
+  if (ep) HIP_TRY(hipMemcpy(s->ep.get() + first, ep, sizeof(int2) * count, hipMemcpyHostToDevice));
+  else HIP_TRY(hipMemset(s->ep.get() + first, 0, sizeof(int2) * count));
+  HIP_TRY(hipMemcpy(s->mt.get() + first * MT_N, mt, sizeof(uint32_t) * MT_N * (size_t)count,
+                    hipMemcpyHostToDevice));
   HIP_TRY(hipDeviceSynchronize());
   return TG_OK;
 }

@@ -306,6 +306,17 @@ struct One {
 
 }  // namespace tg
 
+// a snapshot (tg_amd.h tg_snap): `slots` saved envs of the handle that created it, one array per
+// field of a slot (tg_snapshot.h Snap).  The handle owns it (tg_batch::snaps).
+struct tg_snap {
+  tg_batch* owner = nullptr;
+  int64_t slots = 0;
+  tg::DevBuf<uint4> st4;
+  tg::DevBuf<double2> ang;
+  tg::DevBuf<int2> ep;
+  tg::DevBuf<uint32_t> mt;  // [slots][624]
+};
+
 // the handle (tg_amd.h tg_batch).  Members are destroyed in reverse order after tg_destroy has
 // stopped the server: nothing on the device runs against a buffer that is being freed.
 struct tg_batch {
@@ -350,6 +361,7 @@ struct tg_batch {
   tg::One one;
   std::unique_ptr<tg::RenderState, tg::RenderDelete> rs;  // tg_render_init
   tg::FlowState fl;
+  std::vector<std::unique_ptr<tg_snap>> snaps;  // tg_snap_create's, until tg_snap_destroy
   // read once at tg_create: TG_FLOW_DEBUG (print the census and every k_flow launch's
   // sub-problem counters; synchronises after each launch) and the test hook TG_FLOW_SKIP_PART
   // (sub-problem x's waves leave at once: tests/test_gpu_flow.py checks TG_ERR_FLOW is raised)

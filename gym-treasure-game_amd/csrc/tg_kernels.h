@@ -6,6 +6,7 @@
 #include "tg_dev.h"
 #include "tg_flow.h"
 #include "tg_policy_mlp.h"
+#include "tg_snapshot.h"
 
 namespace {
 
@@ -611,7 +612,7 @@ __global__ __launch_bounds__(BLOCK) void k_predicates(Level L, const uint32_t* _
 
 // tg_read_state's MT part: the generation holding each env's position (CPython's mt[]),
 // envs [first, first + count) -> dst [count][624] (contiguous), 4 words per lane (an odd
-// generation's twisted from the stored one before it)
+// generation's twisted from the stored one before it: tg_snapshot.h snap_gen_quad, k_snap_save's)
 __global__ __launch_bounds__(BLOCK) void k_gather_mt(Soa S, int64_t first, int64_t count,
                                                       uint32_t* __restrict__ dst) {
   constexpr int Q = MT_N / 4;  // 156 uint4 per generation
@@ -620,17 +621,7 @@ __global__ __launch_bounds__(BLOCK) void k_gather_mt(Soa S, int64_t first, int64
   const int64_t k = t / Q;
   const int q = (int)(t - k * Q);
   const int64_t i = first + k;
-  const uint32_t g = (S.st4[i].w & MT_POS_MASK) / (uint32_t)MT_N;
-  const uint32_t* const mt = S.mt + i * MT_STORE;
-  uint4 v;
-  if (g & 1u) {
-    const uint32_t* const prev = mt + mt_store_off(g - 1u);
-    v = make_uint4(twist_at(prev, 4 * q), twist_at(prev, 4 * q + 1), twist_at(prev, 4 * q + 2),
-                   twist_at(prev, 4 * q + 3));
-  } else {
-    v = reinterpret_cast<const uint4*>(mt + mt_store_off(g))[q];
-  }
-  reinterpret_cast<uint4*>(dst)[t] = v;
+  reinterpret_cast<uint4*>(dst)[t] = snap_gen_quad(S.mt + i * MT_STORE, snap_gen(S.st4[i].w), q);
 }
 
 // tg_probe_dispatch: nothing (a dependent kernel boundary's cost alone)

@@ -251,6 +251,8 @@ class TreasureGameVec:
     def close(self):
         if getattr(self, "_h", None) is not None:
             torch.cuda.synchronize(self.device)
+            for s in list(getattr(self, "_snaps", ())):
+                s.close()
             self._L.tg_destroy(self._h)
             self._h = None
 
@@ -748,6 +750,160 @@ class TreasureGameVec:
         """Resume from a ``save`` checkpoint."""
         with np.load(path) as z:
             self.write_state({k: z[k] for k in z.files})
+
+    # -- device-resident snapshots ----------------------------------------------------------------
+    def snapshot(self, slots):
+        """A ``Snapshot`` of ``slots`` saved envs in device memory (tg_snap_create): the
+        reference's ``copy.deepcopy(env)`` for subsets of the batch, without a host copy or a
+        synchronisation.  Closed with the env if not before."""
+        return Snapshot(self, slots)
+
+    def _index(self, x, what):
+        """an index argument as a contiguous int64 tensor on the env's device (converted once)"""
+        if not (isinstance(x, torch.Tensor) and x.dtype == torch.int64 and x.device == self.device
+                and x.is_contiguous()):
+            x = torch.as_tensor(x, device=self.device).to(torch.int64).contiguous()
+        if x.dim() != 1:
+            raise ValueError("%s must be one-dimensional" % what)
+        return x
+
+    def fork(self, src, dst, seeds=None):
+        """Env ``dst[k]`` becomes a copy of env ``src[k]`` (``copy.deepcopy``; with ``seeds``,
+        followed by ``random.seed(seeds[k])``): one save and one load through a scratch snapshot
+        the env keeps, so every source is read before any env is written and ``dst`` may overlap
+        ``src``.  A source may be named any number of times (fan-out).  On the current stream,
+        no synchronisation once the scratch is large enough."""
+        src, dst = self._index(src, "src"), self._index(dst, "dst")
+        k = src.numel()
+        if dst.numel() != k:
+            raise ValueError("src and dst must have the same number of entries")
+        if k == 0:
+            return
+        scratch = getattr(self, "_fork_snap", None)
+        if scratch is None or scratch._s is None or len(scratch) < k:
+            if scratch is not None:
+                scratch.close()
+            self._fork_snap = scratch = Snapshot(self, max(k, 64))
+            self._fork_slots = torch.arange(len(scratch), dtype=torch.int64, device=self.device)
+        slots = self._fork_slots[:k]
+        scratch.save(src, slots)
+        scratch.load(slots, dst, seeds)
+
+
+class Snapshot:
+    """``slots`` saved envs of one ``TreasureGameVec`` in device memory (tg_snap_*): ``save``
+    copies envs into slots and ``load`` slots into envs, through index tensors on the env's
+    device, as kernels on the current stream (no host copy, no synchronisation).  ``read`` and
+    ``write`` move slots to and from the host in ``read_state(mt=True)``'s format, so an archive
+    can outlive the env.  Index arguments are int64 tensors; anything else is converted once."""
+
+    def __init__(self, vec, slots):
+        self._vec = vec
+        self._s = None
+        s = ctypes.c_void_p()
+        check(vec._L.tg_snap_create(vec.handle, int(slots), ctypes.byref(s)), "tg_snap_create")
+        self._s = s
+        self._slots = int(vec._L.tg_snap_slots(s))
+        if not hasattr(vec, "_snaps"):
+            vec._snaps = []
+        vec._snaps.append(self)
+
+    def __len__(self):
+        return self._slots
+
+    @property
+    def handle(self):
+        if self._s is None:
+            raise TgError("snapshot is closed")
+        return self._s
+
+    def close(self):
+        if getattr(self, "_s", None) is not None:
+            if self._vec._h is not None:  # (tg_destroy frees a handle's snapshots itself)
+                self._vec._L.tg_snap_destroy(self._s)
+            self._s = None
+            if self in self._vec._snaps:
+                self._vec._snaps.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 — interpreter teardown
+            pass
+
+    def save(self, envs, slots):
+        """slot ``slots[k]`` <- env ``envs[k]`` as it is at this point of the stream"""
+        v = self._vec
+        envs, slots = v._index(envs, "envs"), v._index(slots, "slots")
+        if envs.numel() != slots.numel():
+            raise ValueError("envs and slots must have the same number of entries")
+        check(v._L.tg_snap_save(v.handle, self.handle, _ptr(envs), _ptr(slots), envs.numel(),
+                                v._stream()), "tg_snap_save")
+
+    def load(self, slots, envs, seeds=None):
+        """env ``envs[k]`` <- slot ``slots[k]``; with ``seeds`` (uint64, or int64 reinterpreted)
+        the env keeps the slot's game state and takes the stream of ``random.seed(seeds[k])``"""
+        v = self._vec
+        envs, slots = v._index(envs, "envs"), v._index(slots, "slots")
+        if envs.numel() != slots.numel():
+            raise ValueError("slots and envs must have the same number of entries")
+        if seeds is not None:
+            if not (isinstance(seeds, torch.Tensor) and seeds.dtype in (torch.int64, torch.uint64)):
+                seeds = torch.from_numpy(np.ascontiguousarray(
+                    np.asarray(seeds.cpu() if isinstance(seeds, torch.Tensor) else seeds)
+                    .astype(np.uint64)).view(np.int64))
+            seeds = seeds.to(v.device).contiguous()
+            if seeds.dim() != 1 or seeds.numel() != envs.numel():
+                raise ValueError("seeds must have one entry per env")
+        check(v._L.tg_snap_load(v.handle, self.handle, _ptr(slots), _ptr(envs), _ptr(seeds),
+                                envs.numel(), v._stream()), "tg_snap_load")
+
+    def _range(self, first, count):
+        first = int(first)
+        count = self._slots - first if count is None else int(count)
+        if first < 0 or count < 0 or first + count > self._slots:
+            raise ValueError("slots [%d, %d) of %d" % (first, first + count, self._slots))
+        return first, count
+
+    def read(self, first=0, count=None):
+        """slots [first, first + count) as a ``read_state(mt=True)``-style dict (synchronises);
+        ``mt_pos`` is what was saved (0..622) or written (0..624)"""
+        first, n = self._range(first, count)
+        out = {"pos": np.zeros((n, 2), np.int32), "flags": np.zeros(n, np.uint32),
+               "objs": np.zeros((n, 4), np.int32), "ang": np.zeros((n, 2), np.float64),
+               "mt": np.zeros((n, 624), np.uint32), "mt_pos": np.zeros(n, np.uint32),
+               "ep": np.zeros((n, 2), np.int32)}
+        check(self._vec._L.tg_snap_read(self.handle, first, n,
+                                        *[out[k].ctypes.data_as(ctypes.c_void_p)
+                                          for k in TreasureGameVec.STATE_KEYS]), "tg_snap_read")
+        return out
+
+    def write(self, state, first=0):
+        """a ``read_state(mt=True)``-style dict of k envs into slots [first, first + k)
+        (synchronises); validated as ``write_state`` validates, and a rejected write changes
+        nothing"""
+        if "flags" not in state:
+            raise KeyError("state lacks 'flags' (use read_state(mt=True))")
+        n = int(np.asarray(state["flags"]).shape[0])
+        first, n = self._range(first, n)
+        shapes = {"pos": (n, 2), "flags": (n,), "objs": (n, 4), "ang": (n, 2), "mt": (n, 624),
+                  "mt_pos": (n,), "ep": (n, 2)}
+        dt = {"pos": np.int32, "flags": np.uint32, "objs": np.int32, "ang": np.float64,
+              "mt": np.uint32, "mt_pos": np.uint32, "ep": np.int32}
+        arrs = {}
+        for k in TreasureGameVec.STATE_KEYS:
+            if k not in state:
+                if k == "ep":
+                    continue
+                raise KeyError("state lacks %r (use read_state(mt=True))" % k)
+            a = np.ascontiguousarray(state[k], dt[k])
+            if a.shape != shapes[k]:
+                raise ValueError("state[%r] has shape %s, expected %s" % (k, a.shape, shapes[k]))
+            arrs[k] = a
+        check(self._vec._L.tg_snap_write(self.handle, first, n,
+                                         *[arrs[k].ctypes.data_as(ctypes.c_void_p)
+                                           if k in arrs else None
+                                           for k in TreasureGameVec.STATE_KEYS]), "tg_snap_write")
 
 
 class GpuOption:

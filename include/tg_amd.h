@@ -381,6 +381,62 @@ int tg_write_state(tg_batch *h, const int32_t *pos, const uint32_t *flags, const
                    const double *ang, const uint32_t *mt, const uint32_t *mt_pos,
                    const int32_t *ep);
 
+/* ---- device-resident snapshots: save, load and fork envs (an extension) ---------------------
+ * The reference idiom is copy.deepcopy(env), optionally followed by random.seed(s): "put env j
+ * into the state env i had then".  A snapshot holds `slots` saved envs in device memory; a slot
+ * is tg_read_state's record of one env (2,536 B: the 16-B state word, the two angles, the
+ * episode's (return, length) and the MT generation holding the position with its index), a tenth
+ * of an env's ring.  tg_snap_save and tg_snap_load move envs to slots and slots to envs through
+ * DEVICE index arrays of `count` entries (env indices local to the handle): they only launch
+ * kernels on `stream`, allocate nothing, copy nothing to the host and never synchronise, so they
+ * can be queued between rollouts; what they need is allocated by tg_snap_create.  count == 0:
+ * TG_OK, nothing launched.
+ *
+ * A snapshot belongs to the handle that created it (same device, same level): any other handle
+ * gets TG_E_INVAL.  Its buffers are counted by tg_live_resources; tg_destroy(h) frees the
+ * snapshots tg_snap_destroy did not.
+ *
+ * tg_snap_save: slot slots[k] receives env envs[k] as it is at that point of the stream (whatever
+ * ring generation it is in, and whether or not a half of its ring awaits regeneration: neither
+ * shows in the slot).  The envs are not changed.
+ * tg_snap_load: env envs[k] becomes slot slots[k]: its game state, its episode (the return and
+ * the length so far: the next finished episode reports them plus its steps after the load, and
+ * tg_set_time_limit counts the length), and its stream, which continues bit for bit as
+ * tg_write_state of the same record would make it continue (index 624 included).  A slot may be
+ * named any number of times (fan-out).  With seeds != NULL env envs[k] takes the slot's game
+ * state and episode, and the stream of random.seed(seeds[k]) (what
+ * random.Random(seeds[k]).getstate() continues): copy.deepcopy(env), then random.seed(s).
+ * Envs a load does not name are untouched: state, stream, pending regeneration and its 16-step
+ * cadence (tg_regenerate) are what they would be without the call.  The episode queue and
+ * tg_get_stats's counters are not touched.
+ * An envs[k] outside [0, N) or a slots[k] outside [0, slots) makes that entry a no-op and sets
+ * TG_ERR_INDEX in what tg_errors reports (a bit of the handle, never of an env's flag word);
+ * nothing is read or written out of bounds.  Two entries of one call that name the same target
+ * (an env in a load, a slot in a save) leave that target unspecified and nothing else written.
+ * TG_E_INVAL, with nothing launched: a null handle, snapshot, envs or slots; count < 0; a
+ * snapshot of another handle; slots <= 0 in tg_snap_create.
+ *
+ * tg_snap_read / tg_snap_write: slots [first, first + count) out to and in from host buffers in
+ * tg_read_state's and tg_write_state's formats, with tg_write_state's validation (mt_pos even and
+ * 0..624, pos within int16, objs within int8; all of write's pointers but ep required, ep NULL =
+ * zeros; any of read's may be NULL).  They synchronise.  A failed write has changed nothing.  A
+ * written record is stored as given and read back verbatim (mt_pos 624 too; a saved one has
+ * 0..622), so an archive persists across handles and runs.  A slot never written holds zeros. */
+#define TG_ERR_INDEX (1u << 31)   /* tg_snap_save / tg_snap_load: an env or slot index out of range */
+typedef struct tg_snap tg_snap;
+int tg_snap_create(tg_batch *h, int64_t slots, tg_snap **out);   /* allocates; synchronises */
+void tg_snap_destroy(tg_snap *s);                                /* also freed by tg_destroy(h) */
+int64_t tg_snap_slots(const tg_snap *s);
+int tg_snap_save(tg_batch *h, tg_snap *s, const int64_t *envs, const int64_t *slots, int64_t count,
+                 void *stream);
+int tg_snap_load(tg_batch *h, const tg_snap *s, const int64_t *slots, const int64_t *envs,
+                 const uint64_t *seeds, int64_t count, void *stream);
+int tg_snap_read(tg_snap *s, int64_t first, int64_t count, int32_t *pos, uint32_t *flags,
+                 int32_t *objs, double *ang, uint32_t *mt, uint32_t *mt_pos, int32_t *ep);
+int tg_snap_write(tg_snap *s, int64_t first, int64_t count, const int32_t *pos,
+                  const uint32_t *flags, const int32_t *objs, const double *ang, const uint32_t *mt,
+                  const uint32_t *mt_pos, const int32_t *ep);
+
 /* ---- render('rgb_array') -----------------------------------------------------------------
  * Sprite sheet: TG_SPR_COUNT RGBA8 images of sprite_w x sprite_h (the reference's PNGs decoded,
  * e.g. by PIL, in this order; the reference scales each to 48x48 at load, DR/:57-134). */
